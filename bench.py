@@ -1,12 +1,19 @@
 #!/usr/bin/env python3
 """Benchmark: disparity Mpix/s at 1080p, num_disp 128 (BASELINE.json metric), frame-sharded
-over N GPUs (one process per GPU), with the dominant kernel's roofline, a parity check of the
-timed matcher against the C oracle, and the CPU baseline (C restatement of the same contract)
-timed on the host.
+over N GPUs (one process per GPU).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2] [--path fused|volume]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline figure needs: set-up, clock settling, the W warmup steps,
+the K timed steps, the outputs of the last timed step if ``--dump-outputs DIR`` is given, and the
+JSON line (``value``, ``ms_per_step``).  ``--full`` adds everything else the line can carry: the
+parity check of the timed matcher against the C oracle, the secondary measurements, the same K
+steps before clock settling, the per-kernel breakdown pass with the dominant kernel's roofline,
+and the CPU baseline (C restatement of the same contract) timed on the host; the ``--no-*``
+options trim a ``--full`` run and have no effect without it.
 
 ``bench.py --gpus N`` without a torch.distributed environment launches the N ranks itself
 (torch.distributed.run as a child process, before anything touches the GPU) and exits with its
@@ -153,6 +160,28 @@ def time_cpu(ref, kw, L, R, threads: int, min_seconds: float, max_frames: int = 
     return L.size * n / dt / 1e6, dt, n
 
 
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs writes at most this much array data in all (files < 64 MB)
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> dict:
+    """--dump-outputs: each array as out_dir/<name>.npy in float32 (int16 x16 values are exact in it).
+    Arrays that together exceed DUMP_BUDGET_BYTES are cut to an equal share each: a fixed, seeded
+    sample of the flattened array (sorted indices, the same for every run of the same shapes)."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // 4 // max(1, len(arrays))
+    total = sum(a.size for a in arrays.values())
+    info = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        sampled = 4 * total > DUMP_BUDGET_BYTES and a.size > share
+        if sampled:
+            idx = np.sort(np.random.default_rng(20240229).choice(a.size, size=share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        info[name] = {"shape": list(a.shape), "dtype": "float32", "sampled": bool(sampled)}
+    return info
+
+
 def free_port() -> int:
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -270,6 +299,12 @@ def main():
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl: one rank per GPU over RCCL (the measured mode); gloo: oversubscribed rehearsal, "
                          "ranks share the visible GPUs (labelled in the JSON line, not a scaling figure)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the oracle parity checks, the secondary measurements, the unsettled K steps, the "
+                         "breakdown pass + roofline and the CPU baseline (default: the headline figure only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs (the int16 x16 map and the "
+                         "float32 map its caller receives) as DIR/<name>.npy, float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-volume-roofline", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="skip the oracle check of frame 0 (tuning runs)")
@@ -373,8 +408,10 @@ def main():
     # from a second handle with event timing, run after the timed region (breakdown pass).
     matcher = HipBlockMatcher(device=local, path=args.path, timing=False, grid_blocks=args.grid_blocks,
                               aggregation=args.sgm, **kw)
-    tmatcher = HipBlockMatcher(device=local, path=args.path, timing=True, grid_blocks=args.grid_blocks,
-                               aggregation=args.sgm, **kw)
+    tmatcher = None
+    if args.full:
+        tmatcher = HipBlockMatcher(device=local, path=args.path, timing=True, grid_blocks=args.grid_blocks,
+                                   aggregation=args.sgm, **kw)
     stream = torch.cuda.current_stream(dev)
 
     def step(i, m=matcher, st=None, of=None, ff=None):
@@ -417,7 +454,7 @@ def main():
     # (oracle/bm_ref.c, the checker; never on the measured path), before the timed region; after it
     # the same handle's frame-0 map is compared with this one again on the device
     parity, ref0 = None, None
-    if not args.no_parity and not args.sgm:
+    if args.full and not args.no_parity and not args.sgm:
         from oracle.cref import CRef
         step(0)
         torch.cuda.synchronize(dev)
@@ -436,8 +473,10 @@ def main():
     # secondary measurements (never `value`) run BEFORE the headline's warmup, so the timed region
     # starts on a GPU that has been busy for seconds (clocks settled) and the long CPU baseline
     # runs after it
-    sec = secondaries(args, cfg, rk, matcher, frames, hostL, hostR, allL, allR, out_fixed, out_float, stream, nres, B,
-                      kw)
+    sec = {}
+    if args.full:
+        sec = secondaries(args, cfg, rk, matcher, frames, hostL, hostR, allL, allR, out_fixed, out_float, stream, nres,
+                          B, kw)
 
     # clock settling (untimed): the GPU's clock follows its load over ~0.1 s, and the 5 warmup steps
     # of the driver's command are 0.4 ms - a 20-step region right after them ran each C2 launch at
@@ -447,7 +486,7 @@ def main():
     # the same K steps once before clock settling (the settled headline is not comparable
     # with round-1/2 lines, which had no settling; this figure is)
     unsettled = None
-    if args.steps > 0:
+    if args.full and args.steps > 0:
         torch.cuda.synchronize(dev)
         rk.barrier()
         torch.cuda.synchronize(dev)
@@ -491,6 +530,12 @@ def main():
     region_ms = ev0.elapsed_time(ev1) / args.steps  # GPU time per step over the timed region
     elapsed = rk.allreduce(float(elapsed), "max")
 
+    dumped = None
+    if args.dump_outputs and args.steps > 0 and rank == 0:
+        # what the caller of the last timed step received: that lane's int16 x16 and float32 maps
+        _, _, of, ff = lanes[(args.steps - 1) % S]
+        dumped = dump_outputs(args.dump_outputs, {"disp_fixed": of.cpu().numpy(), "disp_float": ff.cpu().numpy()})
+
     if ref0 is not None:
         # every timed lane's LAST output of the region (its own handle, in_flight when the lanes carry
         # it) against the oracle map of the frame that step computed
@@ -531,7 +576,9 @@ def main():
     # slow (337 against 298 us under rocprofv3; profiles/r04v_timing_probe.json), and 100 steps read
     # C4's pass 49.1-51.9 us against 48.6-48.9 at 500 (profiles/r04am_breakdown_steps.txt)
     nbd = args.breakdown_steps
-    if args.path == "fused" and cfg["disp12_max_diff"] < 0:
+    if not args.full:
+        ktimes = None
+    elif args.path == "fused" and cfg["disp12_max_diff"] < 0:
         if S == 1:
             ktimes = {"bm_pass_left": (region_ms, args.steps)}
         else:
@@ -568,53 +615,7 @@ def main():
     if rank == 0:
         px_total = H * W * B * args.steps * ws
         value = px_total / elapsed / 1e6
-        ab = algorithmic_bytes(cfg)
-        # dominant kernel of this path (largest total time)
-        dom = max(ktimes.items(), key=lambda kv: kv[1][0] * kv[1][1])
-        dom_name, (dom_ms, dom_n) = dom
-        if len(ktimes) == 1:
-            # one kernel per step: its average launch duration from stream events around back-to-back
-            # launches on one stream (the timed region itself at --streams 1; includes the dispatch gaps)
-            ksrc = ("stream events over the timed region / steps" if S == 1 else
-                    f"stream events over {nbd} back-to-back launches on one stream after the timed region")
-        else:
-            ksrc = f"per-launch HIP events, breakdown pass of {nbd} steps after the timed region"
-        traffic = load_traffic()
-        tr = traffic.get(f"{args.config}:{args.path}:{dom_name}")
-        # one launch covers B frames; a volume-path kernel moves only its own half (K1 writes the volume,
-        # K2 reads it: SURVEY 8(d) per kernel)
-        kbytes = {"cost_volume": ab["k1"], "volume_wta": ab["k2"]}.get(dom_name, ab["frame"])
-        per_launch_bytes = kbytes * (B if dom_name == "bm_pass_left" else 1)
-        equiv = per_launch_bytes / (dom_ms * 1e-3) / 1e9
-        roofline = None
-        if args.path == "fused" and dom_name == "bm_pass_left":
-            roofline = valu_roofline(args.config, f"{args.config}:fused:bm_pass_left", dom_ms, B)
-        if roofline is None:
-            roofline = {"bound": "hbm", "achieved": round(equiv, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": round(equiv / HBM_PEAK_GBS, 4)}
-        roofline.update({
-            "traffic": tr["hbm_bytes_per_launch"] * (B if dom_name == "bm_pass_left" else 1) if tr else None,
-            "traffic_source": tr.get("source") if tr else None,
-            "kernel_name": dom_name, "kernel_ms": round(dom_ms, 5), "launches": dom_n, "kernel_ms_source": ksrc,
-            "kernels_ms": {k: round(v[0], 5) for k, v in ktimes.items()},
-            "region_ms_per_step": round(region_ms, 5),
-        })
-        if S > 1:
-            roofline["region_note"] = (f"region_ms_per_step: {S} frames in flight, so a step's GPU time is below a "
-                                       "launch's own duration (kernel_ms)")
-        if roofline.get("traffic"):
-            hbm = roofline["traffic"] / (dom_ms * 1e-3) / 1e9
-            roofline["hbm_achieved_GBs"] = round(hbm, 1)
-            roofline["hbm_frac_measured"] = round(hbm / HBM_PEAK_GBS, 4)
-        if roofline["bound"] == "valu":
-            roofline["equivalent_hbm"] = {
-                "algorithmic_bytes_per_launch": per_launch_bytes, "achieved": round(equiv, 1), "unit": "GB/s",
-                "frac_of_peak": round(equiv / HBM_PEAK_GBS, 4),
-                "note": "SURVEY 8(d) D3 bytes of a materialised cost volume over the fused kernel's time; the "
-                        "fused kernel never moves these bytes (see traffic), so this is a comparison, not a bound"}
-        else:
-            roofline["algorithmic_bytes_per_launch"] = per_launch_bytes
-            roofline["basis"] = "SURVEY 8(d) D3 per-frame bytes over the dominant kernel"
+        roofline = roofline_of(args, cfg, ktimes, region_ms, B, S, nbd) if ktimes is not None else None
         par = f"frame-sharded x{ws} (RCCL calibration broadcast, no per-frame collectives)"
         if args.dist_backend == "gloo":
             par = (f"frame-sharded x{ws} OVERSUBSCRIBED on {min(ws, rk.ndev)} GPU(s) (gloo rehearsal of the N-rank "
@@ -632,8 +633,10 @@ def main():
             "roofline": roofline,
             "parity": parity,
             "sharding": sharding_info,
-            "order": "parity check -> secondary measurements -> the K steps unsettled -> clock settling -> warmup "
-                     "-> timed region -> breakdown pass -> CPU baseline",
+            "full": args.full,
+            "order": ("parity check -> secondary measurements -> the K steps unsettled -> clock settling -> warmup "
+                      "-> timed region -> breakdown pass -> CPU baseline" if args.full else
+                      "clock settling -> warmup -> timed region"),
             "settle": {"seconds": args.settle, "steps": settle_steps, "timed": False},
             "streams": {"frames_in_flight": S, "in_flight_handles": lane_ifl,
                         "note": "step i runs on HIP stream i mod S with its own handle and output buffers (a frame's "
@@ -645,14 +648,70 @@ def main():
             result["oversubscribed"] = {"ranks": ws, "visible_gpus": rk.ndev,
                                         "note": "ranks share GPUs: value is a rehearsal of the N-rank body, not "
                                                 "N-GPU throughput"}
+        if dumped is not None:
+            result["dump_outputs"] = {"dir": args.dump_outputs, "step": args.steps - 1, "arrays": dumped}
         result.update(sec)
-        if not args.no_cpu_baseline and ws == 1:
+        if args.full and not args.no_cpu_baseline and ws == 1:
             result["cpu_baseline"] = cpu_baseline(args, cfg, hostL[0], hostR[0])
         print(json.dumps(result), file=json_out, flush=True)
 
     matcher.close()
-    tmatcher.close()
+    if tmatcher is not None:
+        tmatcher.close()
     rk.close()
+
+
+def roofline_of(args, cfg, ktimes, region_ms, B, S, nbd) -> dict:
+    """The dominant kernel of the breakdown pass against its bound (--full): the VALU-issue roofline
+    of the fused pass, the HBM roofline of every other kernel."""
+    ab = algorithmic_bytes(cfg)
+    # dominant kernel of this path (largest total time)
+    dom = max(ktimes.items(), key=lambda kv: kv[1][0] * kv[1][1])
+    dom_name, (dom_ms, dom_n) = dom
+    if len(ktimes) == 1:
+        # one kernel per step: its average launch duration from stream events around back-to-back
+        # launches on one stream (the timed region itself at --streams 1; includes the dispatch gaps)
+        ksrc = ("stream events over the timed region / steps" if S == 1 else
+                f"stream events over {nbd} back-to-back launches on one stream after the timed region")
+    else:
+        ksrc = f"per-launch HIP events, breakdown pass of {nbd} steps after the timed region"
+    traffic = load_traffic()
+    tr = traffic.get(f"{args.config}:{args.path}:{dom_name}")
+    # one launch covers B frames; a volume-path kernel moves only its own half (K1 writes the volume,
+    # K2 reads it: SURVEY 8(d) per kernel)
+    kbytes = {"cost_volume": ab["k1"], "volume_wta": ab["k2"]}.get(dom_name, ab["frame"])
+    per_launch_bytes = kbytes * (B if dom_name == "bm_pass_left" else 1)
+    equiv = per_launch_bytes / (dom_ms * 1e-3) / 1e9
+    roofline = None
+    if args.path == "fused" and dom_name == "bm_pass_left":
+        roofline = valu_roofline(args.config, f"{args.config}:fused:bm_pass_left", dom_ms, B)
+    if roofline is None:
+        roofline = {"bound": "hbm", "achieved": round(equiv, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(equiv / HBM_PEAK_GBS, 4)}
+    roofline.update({
+        "traffic": tr["hbm_bytes_per_launch"] * (B if dom_name == "bm_pass_left" else 1) if tr else None,
+        "traffic_source": tr.get("source") if tr else None,
+        "kernel_name": dom_name, "kernel_ms": round(dom_ms, 5), "launches": dom_n, "kernel_ms_source": ksrc,
+        "kernels_ms": {k: round(v[0], 5) for k, v in ktimes.items()},
+        "region_ms_per_step": round(region_ms, 5),
+    })
+    if S > 1:
+        roofline["region_note"] = (f"region_ms_per_step: {S} frames in flight, so a step's GPU time is below a "
+                                   "launch's own duration (kernel_ms)")
+    if roofline.get("traffic"):
+        hbm = roofline["traffic"] / (dom_ms * 1e-3) / 1e9
+        roofline["hbm_achieved_GBs"] = round(hbm, 1)
+        roofline["hbm_frac_measured"] = round(hbm / HBM_PEAK_GBS, 4)
+    if roofline["bound"] == "valu":
+        roofline["equivalent_hbm"] = {
+            "algorithmic_bytes_per_launch": per_launch_bytes, "achieved": round(equiv, 1), "unit": "GB/s",
+            "frac_of_peak": round(equiv / HBM_PEAK_GBS, 4),
+            "note": "SURVEY 8(d) D3 bytes of a materialised cost volume over the fused kernel's time; the "
+                    "fused kernel never moves these bytes (see traffic), so this is a comparison, not a bound"}
+    else:
+        roofline["algorithmic_bytes_per_launch"] = per_launch_bytes
+        roofline["basis"] = "SURVEY 8(d) D3 per-frame bytes over the dominant kernel"
+    return roofline
 
 
 def secondaries(args, cfg, rk, matcher, frames, hostL, hostR, allL, allR, out_fixed, out_float, stream, nres, B,
