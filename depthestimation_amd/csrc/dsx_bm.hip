@@ -3,9 +3,10 @@
 //
 // Work decomposition
 //   * One block = NW waves = Dp disparities. SAD lanes own a disparity PAIR (d0, d0+1) whose
-//     costs live in the two u16 halves of one VGPR (v_pk_{max,min}_u16 for the absolute
-//     differences, carry-free full-rate v_add/sub_u32 for the sums; SAD window sums <= 225*255
-//     fit u16); SSD lanes own one disparity, summed exactly in f32 (FSS below) or u32.
+//     costs live in the two u16 halves of one VGPR (v_sad_u8 / v_sad_hi_u8 on zero-extended bytes
+//     add an absolute difference into the low / high half, carry-free full-rate v_add/sub_u32
+//     for the sums; SAD window sums <= 225*255 fit u16); SSD lanes own one disparity, summed
+//     exactly in f32 (FSS below) or u32.
 //   * The image is cut into vertical strips of TX = 32 output columns.  The (strip, row)
 //     space is split over a persistent grid (blocks = resident capacity; host-computed
 //     partition, bm2_partition), each block
@@ -13,12 +14,13 @@
 //     differences per column per row: the entering and the leaving row), so there is no
 //     tail generation and no per-tile re-initialisation except at segment starts.
 //   * Each row step needs the entering row (y+R+1) and the leaving row (y-R); both are staged
-//     in double-buffered LDS slots.  The searched row is stored as
-//     S[j] = {src(pos(j)), src(pos(j+1))} u16 pairs in "disparity order" (j grows with d),
-//     so a lane reads the pair for its two disparities with one aligned ds_read_b64 per two
-//     columns; the reference row is wave-uniform: it is stored as u16 pairs and read with
-//     broadcast 16-B LDS loads (8 columns), then selected per column with VOP3P op_sel.  The
-//     next step's rows are prefetched from HBM into VGPRs while the current row computes.
+//     in double-buffered LDS slots.  The searched row is stored as one zero-extended dword per
+//     entry, B[j] = src(pos(j)), in "disparity order" (j grows with d): a pair lane's two
+//     disparities take neighbouring entries, and over a row it reads B[d0 .. d0+NC] with one
+//     aligned ds_read_b64 per two columns (+ one dword); the reference row is wave-uniform: it is
+//     stored as one zero-extended dword per column (f32 for FSS) and read with broadcast 16-B
+//     LDS loads (4 columns each).  The next step's rows are prefetched from HBM into VGPRs
+//     while the current row computes.
 //   * Per row the TX x Dp costs go to an LDS tile; the epilogue re-reads it with TPP = 2*NW
 //     lanes per pixel (DSL = Dp/TPP disparities each), finds the minimum with packed block
 //     minima (8 disparities per 16-B read), the lowest winning d with a short scan of the
@@ -58,17 +60,22 @@ __device__ __forceinline__ uint32_t as1(u16x2 v) { return __builtin_bit_cast(uin
 __device__ __forceinline__ int clampi2(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __device__ __forceinline__ uint32_t umin2(uint32_t a, uint32_t b) { return a < b ? a : b; }
 // Packed u16 pairs summed with 32-bit v_add_u32 / v_sub_u32, which issue in 2 cycles against 4 for
-// every v_pk_* op (tools/ubench3.hip).  Exact whenever no half carries or borrows: absolute
-// differences (max - min >= 0), column sums (<= 255 (2R+1)) plus one difference, box sums
-// (<= 57,375) plus one column sum, and results that are themselves non-negative sums.
-__device__ __forceinline__ u16x2 absdiff2(u16x2 a, u16x2 b) {
-    return as2(as1(__builtin_elementwise_max(a, b)) - as1(__builtin_elementwise_min(a, b)));
-}
+// every v_pk_* op (tools/ubench3.hip).  Exact whenever no half carries or borrows: column sums
+// (<= 255 (2R+1)) plus or minus one of their own terms, box sums (<= 57,375) plus one column sum,
+// and results that are themselves non-negative sums.
 __device__ __forceinline__ u16x2 add_sub2(u16x2 a, u16x2 p, u16x2 q) { return as2(as1(a) + as1(p) - as1(q)); }
 // a * b + c on 24-bit signed operands (|a|, |b| <= 255 here): one full-rate v_mad_i32_i24
 __device__ __forceinline__ int mad_i24(int a, int b, int c) {
     int r;
     asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+// c + (|a - b| summed over the 4 bytes << 16): with zero-extended bytes in a and b the absolute
+// difference lands in the high u16 half of a packed pair (v_sad_u8 is the low half's form); both
+// issue in 4.15 cycles (tools/ubench3.hip) against 2 v_pk_* + 2 v_add/sub_u32 for max - min
+__device__ __forceinline__ uint32_t sad_hi_u8(uint32_t a, uint32_t b, uint32_t c) {
+    uint32_t r;
+    asm("v_sad_hi_u8 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
 }
 // min(src of lane l-1, key) with lane 0 keeping key: one v_min_u32_dpp wave_shr:1 whose disabled lane
@@ -98,8 +105,8 @@ struct Geo {
     static constexpr int SROW = rnd16(NJ * 4 + 16);  // >= 16 * ceil(NJ / 4): whole-lane b128 stores
     static constexpr int MAXJ = (NJ + NT - 1) / NT;
     static constexpr int NB = DSL / 8;        // 8-disparity blocks per epilogue lane
-    // reference row (broadcast reads): u16 pairs for SAD, f32 for SSD
-    static constexpr int REFB = SSD ? rnd16(4 * (NC + 8)) : rnd16(2 * (NC + 8));
+    // reference row (broadcast reads): one dword per column (zero-extended byte, f32 for FSS)
+    static constexpr int REFB = rnd16(4 * (NC + 8));
     static constexpr int SLOT = SROW + REFB;
     static constexpr int SMEM0 = 4 * SLOT + TX * PITCH;
     static constexpr int SMEM = SMEM0 > (2 * R + 1) * SLOT ? SMEM0 : (2 * R + 1) * SLOT;
@@ -156,7 +163,7 @@ __device__ __forceinline__ uint32_t gmin(uint32_t v) {
 typedef const __attribute__((address_space(4))) uint32_t cu32;
 
 // One segment: strip x0, rows [yb, ye). FAST: every staged search position lies inside the
-// image (one unaligned dword + one byte load per lane and row); otherwise replicate-clamped
+// image (one unaligned dword load per lane and row); otherwise replicate-clamped
 // byte loads. All per-row state is in plain registers (no structs / arrays with runtime
 // indices, which hipcc would demote to scratch).
 // The LR pass's row loop re-reads the launch arguments from the kernarg segment every row (scalar
@@ -184,8 +191,7 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
 ) {
     using G = Geo<R, SSD, NW>;
     constexpr int TX = G::TX, NC = G::NC, Dp = G::Dp, NT = G::NT, TPP = G::TPP, DSL = G::DSL, CB = G::CB,
-                  PITCH = G::PITCH, NJ = G::NJ, SLOT = G::SLOT, NB = G::NB, NJ4 = (NJ + 3) / 4,
-                  NCH = (NC + 7) / 8;
+                  PITCH = G::PITCH, NJ = G::NJ, SLOT = G::SLOT, NB = G::NB, NJ4 = (NJ + 3) / 4;
     constexpr int side = SIDE;
     // the LR pass reloads the launch arguments per segment too: values derived from them in the
     // segment prologue would otherwise be hoisted out of the block's segment loop and spilled
@@ -201,6 +207,10 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
     constexpr bool FSS = SSD && !ABS && R <= 5 && (SIDE == 0 || SIDE == 3 || SIDE == 4);
     constexpr bool SGK = SIDE == 4;  // left pass + OpenCV-form LR keys (lr_form 'sgbm' on the fused path)
     constexpr uint32_t OFF = FSS ? 0x4B000000u : 0u;
+    // Columns per chunk of the column-sum loops (the staged words of one chunk are in flight
+    // together).  With one dword per reference column the 8-column chunks spill in the LR pass and
+    // the u32 / SAD1 builds, which sit at their register budgets: those take 4, like the FSS row loop.
+    constexpr int CW = (!FSS && (SSD || SIDE == 3)) ? 4 : 8, NCH = (NC + CW - 1) / CW;
     typedef typename std::conditional<FSS, float, typename std::conditional<SSD, uint32_t, u16x2>::type>::type acc_t;
     uint8_t *tile = smem + 4 * SLOT;
 
@@ -226,7 +236,7 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
     const int sgn = side == 1 ? 1 : -1;
 
     // ---- raw row loads (registers) and their LDS stores ----
-    // FAST: w0 = dword of 4 search bytes, w1 = the 5th byte; SLOW: w0..w3 = finished S words
+    // FAST: w0 = dword of 4 search bytes; SLOW: w0..w3 = finished S words
     constexpr int NC4 = (NC + 3) / 4;
     // Branch-free: every lane loads (positions clamped into the row), so no load sits under an
     // exec branch and the compiler never drains vmcnt inside the prefetch; st() stores only the
@@ -246,9 +256,12 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
         }
         if constexpr (FAST) {
             const int tj = min(tid, NJ4 - 1);
-            const uint8_t *p = side == 1 ? srow + PB + 4 * tj : srow + PB - 4 * tj - 3;
+            // The one-wave LR builds (at their register budget) add one int offset: (srow + PB) - 4 * tj
+            // keeps a 64-bit -4 * tj live across the segments, which spilled there.  The two-wave LR
+            // build spills more with this form, so the others keep theirs.
+            const uint8_t *p = side == 1 ? srow + PB + 4 * tj
+                                         : (SIDE == 3 && NW == 1) ? srow + (PB - 4 * tj - 3) : srow + PB - 4 * tj - 3;
             w0 = *reinterpret_cast<const uint32_t *>(p);
-            w1 = side == 1 ? p[4] : p[-1];
         } else {
             uint32_t v[4];
             // The one-wave SAD LR builds recompute 4 * tid per load: hoisted, the 4 clamped indices
@@ -263,7 +276,6 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
                 const int j = min(t4 + q, NJ - 1);
                 const int pp = PB + sgn * j;
                 uint32_t t = srow[clampi2(pp, 0, W - 1)];
-                if constexpr (!SSD) t |= (uint32_t)srow[clampi2(pp + sgn, 0, W - 1)] << 16;
                 if constexpr (FSS) t = __float_as_uint((float)t);
                 v[q] = t;
             }
@@ -279,44 +291,29 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
                 make_uint4(__float_as_uint((float)(rf & 0xFFu)), __float_as_uint((float)((rf >> 8) & 0xFFu)),
                            __float_as_uint((float)((rf >> 16) & 0xFFu)), __float_as_uint((float)(rf >> 24)));
         } else if (tid < NC4) {
-            const uint32_t r01 = __builtin_amdgcn_perm(0u, rf, 0x0C010C00u);  // {ref[4t], ref[4t+1]} as u16
-            const uint32_t r23 = __builtin_amdgcn_perm(0u, rf, 0x0C030C02u);
-            *reinterpret_cast<uint2 *>(smem + sl * SLOT + G::SROW + 8 * tid) = make_uint2(r01, r23);
+            *reinterpret_cast<uint4 *>(smem + sl * SLOT + G::SROW + 16 * tid) =
+                make_uint4(rf & 0xFFu, (rf >> 8) & 0xFFu, (rf >> 16) & 0xFFu, rf >> 24);
         }
         if constexpr (FAST) {
-            const uint32_t dw = w0, e = w1;
-            if constexpr (SSD) {
-                if (side == 1) {
-                    w0 = dw & 0xFFu; w1 = (dw >> 8) & 0xFFu; w2 = (dw >> 16) & 0xFFu; w3 = dw >> 24;
-                } else if constexpr (FSS) {  // v_cvt_f32_ubyte{3,2,1,0}
-                    w0 = __float_as_uint((float)(dw >> 24)); w1 = __float_as_uint((float)((dw >> 16) & 0xFFu));
-                    w2 = __float_as_uint((float)((dw >> 8) & 0xFFu)); w3 = __float_as_uint((float)(dw & 0xFFu));
-                } else {
-                    w0 = dw >> 24; w1 = (dw >> 16) & 0xFFu; w2 = (dw >> 8) & 0xFFu; w3 = dw & 0xFFu;
-                }
+            const uint32_t dw = w0;  // byte k = entry 4 tid + k (right) / 4 tid + 3 - k (left)
+            if (side == 1) {
+                w0 = dw & 0xFFu; w1 = (dw >> 8) & 0xFFu; w2 = (dw >> 16) & 0xFFu; w3 = dw >> 24;
+            } else if constexpr (FSS) {  // v_cvt_f32_ubyte{3,2,1,0}
+                w0 = __float_as_uint((float)(dw >> 24)); w1 = __float_as_uint((float)((dw >> 16) & 0xFFu));
+                w2 = __float_as_uint((float)((dw >> 8) & 0xFFu)); w3 = __float_as_uint((float)(dw & 0xFFu));
             } else {
-                if (side == 1) {
-                    w0 = __builtin_amdgcn_perm(e, dw, 0x0C010C00u);
-                    w1 = __builtin_amdgcn_perm(e, dw, 0x0C020C01u);
-                    w2 = __builtin_amdgcn_perm(e, dw, 0x0C030C02u);
-                    w3 = __builtin_amdgcn_perm(e, dw, 0x0C040C03u);
-                } else {
-                    w0 = __builtin_amdgcn_perm(e, dw, 0x0C020C03u);
-                    w1 = __builtin_amdgcn_perm(e, dw, 0x0C010C02u);
-                    w2 = __builtin_amdgcn_perm(e, dw, 0x0C000C01u);
-                    w3 = __builtin_amdgcn_perm(e, dw, 0x0C040C00u);
-                }
+                w0 = dw >> 24; w1 = (dw >> 16) & 0xFFu; w2 = (dw >> 8) & 0xFFu; w3 = dw & 0xFFu;
             }
         }
         if (tid < NJ4) *reinterpret_cast<uint4 *>(smem + sl * SLOT + 16 * tid) = make_uint4(w0, w1, w2, w3);
     };
-    // reference pixels of slot sl, columns [c0, c0+8): one broadcast 16-B LDS read (u16 pairs)
-    auto ref_chunk = [&](int sl, int c0, uint32_t(&rw)[4]) __attribute__((always_inline)) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(smem + sl * SLOT + G::SROW + 2 * c0);
-        rw[0] = v.x;
-        rw[1] = v.y;
-        rw[2] = v.z;
-        rw[3] = v.w;
+    // reference pixels of slot sl, columns [c0, c0+CW): broadcast 16-B LDS reads
+    auto ref_chunk = [&](int sl, int c0, uint32_t(&rw)[CW]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int c = 0; c < CW; c += 4) {
+            const uint4 v = *reinterpret_cast<const uint4 *>(smem + sl * SLOT + G::SROW + 4 * (c0 + c));
+            rw[c] = v.x; rw[c + 1] = v.y; rw[c + 2] = v.z; rw[c + 3] = v.w;
+        }
     };
     // FSS: 8 f32 reference pixels, two broadcast 16-B reads
     auto ref_chunkf = [&](int sl, int c0, float(&rw)[8]) __attribute__((always_inline)) {
@@ -325,43 +322,55 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
         rw[0] = __uint_as_float(v0.x); rw[1] = __uint_as_float(v0.y); rw[2] = __uint_as_float(v0.z); rw[3] = __uint_as_float(v0.w);
         rw[4] = __uint_as_float(v1.x); rw[5] = __uint_as_float(v1.y); rw[6] = __uint_as_float(v1.z); rw[7] = __uint_as_float(v1.w);
     };
-    auto refpk = [](const uint32_t(&rw)[4], int c) __attribute__((always_inline)) -> u16x2 {
-        const u16x2 v = as2(rw[c >> 1]);
-        return (c & 1) ? v.yy : v.xx;
-    };
-    auto refv = [](const uint32_t(&rw)[4], int c) __attribute__((always_inline)) -> uint32_t {
-        return (c & 1) ? (rw[c >> 1] >> 16) : (rw[c >> 1] & 0xFFFFu);
-    };
-    // this lane's S words for columns [c0, c0+8) of slot sl
-    auto s_chunk = [&](int sl, int c0, uint32_t(&sw)[8]) __attribute__((always_inline)) {
+    // this lane's S words for columns [c0, c0+CW) of slot sl: sw[c] is column c0+c's entry for d0 and,
+    // pair layout, sw[c+1] the one for d0+1 (CW+1 entries: aligned 8-B reads + 1 dword).  The left
+    // form's entries run down with c, so they are stored reversed and the extra one (sw[0]) is the
+    // previous chunk's last entry: nx carries it from chunk to chunk (read at c0 == 0).
+    auto s_chunk = [&](int sl, int c0, uint32_t(&sw)[CW + 1], uint32_t &nx) __attribute__((always_inline)) {
         const uint8_t *base = smem + sl * SLOT + d0 * 4;
         if constexpr (side == 1) {
             if constexpr (SSD) {
 #pragma unroll
-                for (int c = 0; c < 8; ++c) sw[c] = *reinterpret_cast<const uint32_t *>(base + (c0 + c) * 4);
+                for (int c = 0; c < CW; ++c) sw[c] = *reinterpret_cast<const uint32_t *>(base + (c0 + c) * 4);
             } else {
                 base = (const uint8_t *)__builtin_assume_aligned(base, 8);
 #pragma unroll
-                for (int c = 0; c < 8; c += 2) {
-                    const uint2 v = *reinterpret_cast<const uint2 *>(base + (c0 + c) * 4);
-                    sw[c] = v.x;
-                    sw[c + 1] = v.y;
+                for (int c = 0; c < CW; c += 2) {
+                    if (c0 + c < NC) {
+                        const uint2 v = *reinterpret_cast<const uint2 *>(base + (c0 + c) * 4);
+                        sw[c] = v.x;
+                        sw[c + 1] = v.y;
+                    }
                 }
+                const int ce = NC - c0 < CW ? NC - c0 : CW;  // one past the chunk's last column
+                sw[ce] = *reinterpret_cast<const uint32_t *>(base + (c0 + ce) * 4);
             }
         } else {
             if constexpr (SSD) {
 #pragma unroll
-                for (int c = 0; c < 8; ++c) sw[c] = *reinterpret_cast<const uint32_t *>(base + (NC - 1 - c0 - c) * 4);
+                for (int c = 0; c < CW; ++c) sw[c] = *reinterpret_cast<const uint32_t *>(base + (NC - 1 - c0 - c) * 4);
             } else {
+                // column c0+c: B[d0 + NC-1-c0-c] = sw[c+1] (d0) and B[d0 + NC-c0-c] = sw[c] (d0+1)
                 base = (const uint8_t *)__builtin_assume_aligned(base, 8);
+                sw[0] = c0 == 0 ? *reinterpret_cast<const uint32_t *>(base + NC * 4) : nx;
 #pragma unroll
-                for (int c = 1; c < 8; c += 2) {
-                    const uint2 v = *reinterpret_cast<const uint2 *>(base + (NC - 1 - c0 - c) * 4);
-                    sw[c] = v.x;
-                    sw[c - 1] = v.y;
+                for (int c = 1; c < CW; c += 2) {
+                    if (c0 + c < NC) {
+                        const uint2 v = *reinterpret_cast<const uint2 *>(base + (NC - 1 - c0 - c) * 4);
+                        sw[c + 1] = v.x;
+                        sw[c] = v.y;
+                        nx = v.x;
+                    }
                 }
             }
         }
+    };
+    // the pair's entries for column c0+c: e0 for d0, e1 for d0+1
+    auto pair_e0 = [](const uint32_t(&sw)[CW + 1], int c) __attribute__((always_inline)) -> uint32_t {
+        return side == 1 ? sw[c] : sw[c + 1];
+    };
+    auto pair_e1 = [](const uint32_t(&sw)[CW + 1], int c) __attribute__((always_inline)) -> uint32_t {
+        return side == 1 ? sw[c + 1] : sw[c];
     };
 
     // ---- segment init: column sums over rows yb-R .. yb+R ----
@@ -512,28 +521,28 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
     block_sync<NW>();
 #pragma unroll 1
     for (int i = 0; i <= 2 * R; ++i) {  // runtime loop: a full unroll makes compile time explode
+        uint32_t nx = 0;
 #pragma unroll
         for (int q = 0; q < NCH; ++q) {
-            const int c0 = 8 * q;
-            uint32_t sw[8], rw[4];
+            const int c0 = CW * q;
+            uint32_t sw[CW + 1], rw[CW];
             float rf8[8];
-            s_chunk(i, c0, sw);
+            s_chunk(i, c0, sw, nx);
             if constexpr (FSS) ref_chunkf(i, c0, rf8);
             else ref_chunk(i, c0, rw);
 #pragma unroll
-            for (int c = 0; c < 8; ++c) {
+            for (int c = 0; c < CW; ++c) {
                 if (c0 + c < NC) {
                     if constexpr (FSS) {
                         const float t = rf8[c] - __uint_as_float(sw[c]);
                         cs[c0 + c] = __builtin_fmaf(t, t, cs[c0 + c]);
                     } else if constexpr (ABS) {
-                        cs[c0 + c] = __builtin_amdgcn_sad_u16(refv(rw, c), sw[c], cs[c0 + c]);  // + |ref - src|
+                        cs[c0 + c] = __builtin_amdgcn_sad_u16(rw[c], sw[c], cs[c0 + c]);  // + |ref - src|
                     } else if constexpr (SSD) {
-                        const int t = (int)refv(rw, c) - (int)sw[c];
+                        const int t = (int)rw[c] - (int)sw[c];
                         cs[c0 + c] += (uint32_t)__mul24(t, t);  // v_mul_i32_i24: |t| <= 255
-                    } else {
-                        const u16x2 Lp = refpk(rw, c), sv = as2(sw[c]);
-                        cs[c0 + c] = as2(as1(cs[c0 + c]) + as1(absdiff2(Lp, sv)));
+                    } else {  // + |ref - src(d0)| in the low half, + |ref - src(d0+1)| in the high half
+                        cs[c0 + c] = as2(sad_hi_u8(rw[c], pair_e1(sw, c), __builtin_amdgcn_sad_u8(rw[c], pair_e0(sw, c), as1(cs[c0 + c]))));
                     }
                 }
             }
@@ -611,31 +620,34 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
             }
           }
         } else if (y > yb) {
+            uint32_t nxn = 0, nxo = 0;
 #pragma unroll
             for (int q = 0; q < NCH; ++q) {
-                const int c0 = 8 * q;
-                uint32_t sn[8], so[8], rn[4], ro[4];
+                const int c0 = CW * q;
+                uint32_t sn[CW + 1], so[CW + 1], rn[CW], ro[CW];
                 ref_chunk(par, c0, rn);
                 ref_chunk(par + 1, c0, ro);
-                s_chunk(par, c0, sn);
-                s_chunk(par + 1, c0, so);
+                s_chunk(par, c0, sn, nxn);
+                s_chunk(par + 1, c0, so, nxo);
 #pragma unroll
-                for (int c = 0; c < 8; ++c) {
+                for (int c = 0; c < CW; ++c) {
                     if (c0 + c < NC) {
                         if constexpr (ABS) {  // cs + |tn| - |to|: two v_sad_u16 (bytes) + one v_sub
-                            cs[c0 + c] = __builtin_amdgcn_sad_u16(refv(rn, c), sn[c], cs[c0 + c]) -
-                                         __builtin_amdgcn_sad_u16(refv(ro, c), so[c], 0u);
+                            cs[c0 + c] = __builtin_amdgcn_sad_u16(rn[c], sn[c], cs[c0 + c]) -
+                                         __builtin_amdgcn_sad_u16(ro[c], so[c], 0u);
                         } else if constexpr (SSD) {  // u32 SSD (R > 5 or the right / volume passes)
-                            const int tn = (int)refv(rn, c) - (int)sn[c];
-                            const int to = (int)refv(ro, c) - (int)so[c];
-                            const int nto = (int)so[c] - (int)refv(ro, c);
+                            const int tn = (int)rn[c] - (int)sn[c];
+                            const int to = (int)ro[c] - (int)so[c];
+                            const int nto = (int)so[c] - (int)ro[c];
                             // two v_mad_i32_i24 (cs + tn^2 + to * (-to)), not the 64-bit
                             // v_mad_u64_u32 that plain int products lowered to
                             cs[c0 + c] = (uint32_t)mad_i24(to, nto, mad_i24(tn, tn, (int)cs[c0 + c]));
                         } else {
-                            const u16x2 Lnp = refpk(rn, c), Lop = refpk(ro, c);
-                            const u16x2 vn = as2(sn[c]), vo = as2(so[c]);
-                            cs[c0 + c] = add_sub2(cs[c0 + c], absdiff2(Lnp, vn), absdiff2(Lop, vo));
+                            // entering row into cs, leaving row summed apart and subtracted: each
+                            // half of it is a term of that half of cs, so nothing borrows
+                            const uint32_t en = sad_hi_u8(rn[c], pair_e1(sn, c), __builtin_amdgcn_sad_u8(rn[c], pair_e0(sn, c), as1(cs[c0 + c])));
+                            const uint32_t lo = sad_hi_u8(ro[c], pair_e1(so, c), __builtin_amdgcn_sad_u8(ro[c], pair_e0(so, c), 0u));
+                            cs[c0 + c] = as2(en - lo);
                         }
                     }
                 }

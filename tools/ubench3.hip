@@ -52,6 +52,7 @@ DEF3(k_perm_b32, "v_perm_b32")
 DEF3(k_pk_mad_u16, "v_pk_mad_u16")
 DEF3(k_mad_u32_u24, "v_mad_u32_u24")
 DEF3(k_msad_u8, "v_msad_u8")
+DEF3(k_sad_hi_u8, "v_sad_hi_u8")
 
 // 64-bit accumulator forms: INS d[2], s0[2], s1, d[2] (quad SAD) or d[2], s0[2], s1[2] (packed f32)
 #define DEFQ(NAME, INS, TAIL)                                                                      \
@@ -100,7 +101,7 @@ int main() {
     {"v_pk_add_f16", k_pk_add_f16}, {"v_pk_max_f16", k_pk_max_f16}, {"v_max_f32", k_max_f32},
     {"v_fma_f32", k_fma_f32}, {"v_sad_u8", k_sad_u8}, {"v_add3_u32", k_add3_u32}, {"v_min3_u32", k_min3_u32},
     {"v_perm_b32", k_perm_b32}, {"v_pk_mad_u16", k_pk_mad_u16}, {"v_mad_u32_u24", k_mad_u32_u24},
-    {"v_msad_u8", k_msad_u8}, {"v_qsad_pk_u16_u8", k_qsad}, {"v_mqsad_pk_u16_u8", k_mqsad},
+    {"v_msad_u8", k_msad_u8}, {"v_sad_hi_u8", k_sad_hi_u8}, {"v_qsad_pk_u16_u8", k_qsad}, {"v_mqsad_pk_u16_u8", k_mqsad},
     {"v_pk_add_f32", k_pk_add_f32}, {"v_pk_mul_f32", k_pk_mul_f32}};
   for (auto &x : ks) {
     const float ms = time_kernel(x.k, buf, blocks, threads);
