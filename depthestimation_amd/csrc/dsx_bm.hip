@@ -54,6 +54,14 @@ constexpr int kWpeSsd = 4;  // SSD blocks of >= 4 waves
 namespace dsx {
 
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+// One 8-B LDS read that stays one: a volatile load in the LDS address space is not paired by the
+// load/store optimiser, which otherwise merges two neighbouring ds_read_b64 into one ds_read2_b64
+// (8 LDS-array cycles per wave against 2 + 2).  The address space must be named: a plain volatile
+// pointer turns the read into a flat load.
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ u32x2 lds_read_b64(const uint8_t *p) {
+    return *(const volatile __attribute__((address_space(3))) u32x2 *)p;
+}
 
 __device__ __forceinline__ u16x2 as2(uint32_t v) { return __builtin_bit_cast(u16x2, v); }
 __device__ __forceinline__ uint32_t as1(u16x2 v) { return __builtin_bit_cast(uint32_t, v); }
@@ -72,11 +80,10 @@ __device__ __forceinline__ int mad_i24(int a, int b, int c) {
 }
 // c + (|a - b| summed over the 4 bytes << 16): with zero-extended bytes in a and b the absolute
 // difference lands in the high u16 half of a packed pair (v_sad_u8 is the low half's form); both
-// issue in 4.15 cycles (tools/ubench3.hip) against 2 v_pk_* + 2 v_add/sub_u32 for max - min
+// issue in 4.15 cycles (tools/ubench3.hip) against 2 v_pk_* + 2 v_add/sub_u32 for max - min.  The
+// builtin (not inline asm) is an instruction the scheduler can see and move.
 __device__ __forceinline__ uint32_t sad_hi_u8(uint32_t a, uint32_t b, uint32_t c) {
-    uint32_t r;
-    asm("v_sad_hi_u8 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
+    return __builtin_amdgcn_sad_hi_u8(a, b, c);
 }
 // min(src of lane l-1, key) with lane 0 keeping key: one v_min_u32_dpp wave_shr:1 whose disabled lane
 // (bound_ctrl off) keeps the tied key.  Written out because hipcc re-associates the builtin form into
@@ -161,6 +168,8 @@ __device__ __forceinline__ uint32_t gmin(uint32_t v) {
 
 
 typedef const __attribute__((address_space(4))) uint32_t cu32;
+typedef const __attribute__((address_space(1))) uint8_t gu8;    // global memory, named for ld()
+typedef const __attribute__((address_space(1))) uint32_t gu32;
 
 // One segment: strip x0, rows [yb, ye). FAST: every staged search position lies inside the
 // image (one unaligned dword load per lane and row); otherwise replicate-clamped
@@ -241,27 +250,52 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
     // Branch-free: every lane loads (positions clamped into the row), so no load sits under an
     // exec branch and the compiler never drains vmcnt inside the prefetch; st() stores only the
     // lanes that own staged words.
+    // RL2: the row loop's second form - scalar row bases in ld, a prefetch on every
+    // step and staging ahead of the step's output stores.  The pair layout takes it (C2 -9 %, C5
+    // -8 %, C4 +4 % in flight, C2r +1 %); the one-disparity layouts measured slower with it (C3
+    // 322.7 -> 330 us, C1 13.19 -> 13.24 us) and keep the first form.
+    constexpr bool RL2 = !SSD;
     auto ld = [&](int r, uint32_t &w0, uint32_t &w1, uint32_t &w2, uint32_t &w3, uint32_t &rf) __attribute__((always_inline)) {
         const int yy = clampi2(r, 0, H - 1);
-        const uint8_t *srow = a.src + fin + (long)yy * stride;
-        const uint8_t *rrow = a.ref + fin + (long)yy * stride;
+        // The row base is wave-uniform and the lane's part a small non-negative offset (FAST:
+        // x0 - R + 4 tr >= 0, PB - 4 tj - 3 >= 1, PB + 4 tj >= 0 by the segment's FAST test; clamped:
+        // an index in [0, W-1]), added as an unsigned 32-bit value: the loads take the scalar-base
+        // form.  The base is pinned to SGPRs - left free, hipcc folds the lane's part into a hoisted
+        // 64-bit per-lane base and pays one v_mad_u64_u32 (yy * stride + base) per load and step.
+        // (the address space is named again behind the asm, or the loads come out as flat loads)
+        // Pair layout only (RL2): the one-disparity layouts keep per-lane 64-bit addresses.
+        const uint8_t *srow_ = a.src + fin + (long)yy * stride;
+        const uint8_t *rrow_ = a.ref + fin + (long)yy * stride;
+        if constexpr (RL2) {
+            asm("" : "+s"(srow_));
+            asm("" : "+s"(rrow_));
+        }
+        typedef typename std::conditional<RL2, gu8, const uint8_t>::type row8;
+        typedef typename std::conditional<RL2, gu32, const uint32_t>::type row32;
+        typedef typename std::conditional<RL2, uint32_t, int>::type rix;
+        row8 *srow = (row8 *)srow_, *rrow = (row8 *)rrow_;
         const int tr = min(tid, NC4 - 1);
         if constexpr (FAST) {
-            rf = *reinterpret_cast<const uint32_t *>(rrow + x0 - R + 4 * tr);
+            if constexpr (RL2) rf = *reinterpret_cast<row32 *>(rrow + (uint32_t)(x0 - R + 4 * tr));
+            else rf = *reinterpret_cast<row32 *>(rrow + x0 - R + 4 * tr);
         } else {
             uint32_t v = 0;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) v |= (uint32_t)rrow[clampi2(x0 - R + 4 * tr + q, 0, W - 1)] << (8 * q);
+            for (int q = 0; q < 4; ++q) v |= (uint32_t)rrow[(rix)clampi2(x0 - R + 4 * tr + q, 0, W - 1)] << (8 * q);
             rf = v;
         }
         if constexpr (FAST) {
             const int tj = min(tid, NJ4 - 1);
-            // The one-wave LR builds (at their register budget) add one int offset: (srow + PB) - 4 * tj
-            // keeps a 64-bit -4 * tj live across the segments, which spilled there.  The two-wave LR
-            // build spills more with this form, so the others keep theirs.
-            const uint8_t *p = side == 1 ? srow + PB + 4 * tj
-                                         : (SIDE == 3 && NW == 1) ? srow + (PB - 4 * tj - 3) : srow + PB - 4 * tj - 3;
-            w0 = *reinterpret_cast<const uint32_t *>(p);
+            row8 *p;
+            if constexpr (RL2) {
+                p = side == 1 ? srow + (uint32_t)(PB + 4 * tj) : srow + (uint32_t)(PB - 4 * tj - 3);
+            } else {
+                // The one-wave LR builds (at their register budget) add one int offset: (srow + PB) - 4 * tj
+                // keeps a 64-bit -4 * tj live across the segments, which spilled there.
+                p = side == 1 ? srow + PB + 4 * tj : (SIDE == 3 && NW == 1) ? srow + (PB - 4 * tj - 3) : srow + PB - 4 * tj - 3;
+            }
+            w0 = *reinterpret_cast<row32 *>(p);
+            if constexpr (RL2) w1 = w2 = w3 = 0;  // st() rebuilds them from w0 (first form: the caller's zeros)
         } else {
             uint32_t v[4];
             // The one-wave SAD LR builds recompute 4 * tid per load: hoisted, the 4 clamped indices
@@ -275,7 +309,7 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
             for (int q = 0; q < 4; ++q) {
                 const int j = min(t4 + q, NJ - 1);
                 const int pp = PB + sgn * j;
-                uint32_t t = srow[clampi2(pp, 0, W - 1)];
+                uint32_t t = srow[(rix)clampi2(pp, 0, W - 1)];
                 if constexpr (FSS) t = __float_as_uint((float)t);
                 v[q] = t;
             }
@@ -337,7 +371,7 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
 #pragma unroll
                 for (int c = 0; c < CW; c += 2) {
                     if (c0 + c < NC) {
-                        const uint2 v = *reinterpret_cast<const uint2 *>(base + (c0 + c) * 4);
+                        const u32x2 v = lds_read_b64(base + (c0 + c) * 4);
                         sw[c] = v.x;
                         sw[c + 1] = v.y;
                     }
@@ -356,7 +390,7 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
 #pragma unroll
                 for (int c = 1; c < CW; c += 2) {
                     if (c0 + c < NC) {
-                        const uint2 v = *reinterpret_cast<const uint2 *>(base + (NC - 1 - c0 - c) * 4);
+                        const u32x2 v = lds_read_b64(base + (NC - 1 - c0 - c) * 4);
                         sw[c + 1] = v.x;
                         sw[c] = v.y;
                         nx = v.x;
@@ -378,12 +412,14 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
 #pragma unroll
     for (int c = 0; c < NC; ++c) cs[c] = acc_t(0);
     // Measured per instantiation (r02, tools/si_ab.sh, same box): C1 (R=2) 20.5 -> 19.5 us, C4 (R=2)
-    // 57.3 -> 56.3 us, C5 (R=7) 610 -> 581 us; but the R=4 instantiation (C2) runs 72.9 -> 79.0 us
-    // with it - its row loop is scheduled worse (more full vmcnt drains), not its init - so R=4 keeps
-    // the row-by-row init.
+    // 57.3 -> 56.3 us, C5 (R=7) 610 -> 581 us.  The R=4 instantiation (C2) once ran 72.9 -> 79.0 us
+    // with it, because its row loop then scheduled worse (full vmcnt drains); with the row loop's
+    // staging ahead of its stores that no longer holds and R=4 gains as well (C2 60.6 -> 59.1 us,
+    // C2r 98.5 -> 95.5 us).  The R=4 LR pass (C2r) still keeps the row-by-row init: at its
+    // 168-VGPR budget the transposed form spills 24 B of values held across the segments.
     // SAD1 (ABS, one disparity per lane) takes the same transposed init with one v_sad_u8 per column
     // and row group (the pair's first entry only)
-    constexpr bool SADINIT = ABS || R != 4;
+    constexpr bool SADINIT = ABS || R != 4 || SIDE != 3;
     if constexpr ((!SSD || ABS) && side != 1 && SADINIT) {
         // SAD (left / volume passes): rows in groups of 4, bytes transposed so that one v_sad_u8
         // sums a column's 4 row terms for one disparity: TP_g[j] = {P(j), P(j+1)} with P(j) the
@@ -589,9 +625,13 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
         }
         const int par = (y & 1) * 2;  // slots {par, par+1} = {new row y+R, old row y-R-1}
         const bool more = y + 1 < ye;
-        // prefetch the next step's entering / leaving rows (+ its dR segment); lands during this step
+        // prefetch the next step's entering / leaving rows (+ its dR segment); lands during this step.
+        // RL2: issued on every step, the segment's last one included - ld clamps the row into
+        // [0, H-1], so that step loads a valid row which nobody stores, and the zero initialisers
+        // are dead.  First form (!RL2): under `if (more)`; writing the zeros then waits for the
+        // previous step's loads and stores (s_waitcnt vmcnt(0) at the loop header).
         uint32_t pn0 = 0, pn1 = 0, pn2 = 0, pn3 = 0, pnr = 0, po0 = 0, po1 = 0, po2 = 0, po3 = 0, por = 0;
-        if (more) {
+        if (RL2 || more) {
             ld(y + 1 + R, pn0, pn1, pn2, pn3, pnr);
             ld(y - R, po0, po1, po2, po3, por);
         }
@@ -811,6 +851,19 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
         DSX_STAMP(3);
         block_sync<NW>();
         DSX_STAMP(4);
+        // The prefetched rows go to LDS here, before the epilogue's output stores: the loads have
+        // had the column update and the box phase to land, and no store is younger than them, so
+        // the waits below never drain a store (after the epilogue they came out as vmcnt(1) / (0)
+        // behind the step's two stores, a full store round trip per row).  Safe: slots par ^ 2 and
+        // (par ^ 2) + 1 were last read by the column update of step y - 1, every wave of the
+        // block has passed the mid-step barrier above since then, and the barrier that ends the
+        // step orders these writes before step y + 1 reads them (the end barrier of step y - 1 alone
+        // already separates them from their last readers).  The epilogue reads the tile only.
+        if (RL2 && more) {
+            st(par ^ 2, pn0, pn1, pn2, pn3, pnr);
+            st((par ^ 2) + 1, po0, po1, po2, po3, por);
+        }
+        DSX_STAMP(5);
         if constexpr (side == 2) {
             // ---- cost volume store: TX pixels x Dp costs, 16-B chunks ----
             constexpr int CPP = Dp * CB / 16;
@@ -986,8 +1039,7 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
                 }
             }
         }
-        DSX_STAMP(5);
-        if (more) {
+        if (!RL2 && more) {  // first form: staged behind the epilogue
             st(par ^ 2, pn0, pn1, pn2, pn3, pnr);
             st((par ^ 2) + 1, po0, po1, po2, po3, por);
         }

@@ -1,0 +1,206 @@
+"""Row loop of the fused block-matching pass (csrc/dsx_bm.hip) after its reordering: the next
+step's rows are prefetched on every step (the segment's last one included, row clamped into the
+frame), staged into LDS directly behind the mid-step barrier - before the epilogue's output stores -
+and loaded through a wave-uniform row base plus an unsigned 32-bit lane offset.
+
+Every comparison is bit for bit over all pixels, on the int16 x16 map and on the float map (float
+mode 'fixed': the x16 value / 16, exact in f32).  The plain left pass, the left pass with the
+uniqueness and left-right checks (lr_form 'bm') and the volume path take the C oracle
+(oracle/cref.py); OpenCV's LR form and the right map take the numpy oracle on the same block costs
+(oracle/sgbm_post.wta_sgbm, oracle/stereo_bm.right_argmin).
+
+Shapes: W = 256, H <= 40.  At D = 128, R = 4 the strips x0 = 160 and 192 stage their rows with the
+unaligned-dword loads and the others with clamped bytes, so both copies of the loop run.
+  * segment ends / the unguarded prefetch: H = 1, 2, 2R+1, 2R+2, 40; grid_blocks 0, 1, 7 and
+    strips x H (every segment a single row: each step is a first and a last step);
+  * the staging slots' parity with several waves per block: SAD at D = 131 (two waves, odd range,
+    padding disparities) and 192 (four waves), SSD in f32 (block 5, 11 at D = 128, 256) and u32
+    (block 13);
+  * every side that shares the loop (left, left + LR 'bm', left + LR 'sgbm', right map, volume) at
+    block sizes 5, 9, 15;
+  * address forms: min_disp 0, 5, -3; two frames per launch (a block's segments cross the frame
+    boundary, non-zero frame offset); rows padded to a stride other than W;
+  * three in-flight handles on three streams, each output against its own frame's oracle.
+Inputs: the seeded random pair and the two carry stressors of tests/test_gpu_bytesad.py."""
+from __future__ import annotations
+
+import numpy as np
+import pytest
+
+from depthestimation_amd.synthetic import stereo_pair
+from oracle.cref import CRef
+from oracle.sgbm_post import wta_sgbm
+from oracle.stereo_bm import cost_volume, right_argmin
+
+pytestmark = pytest.mark.gpu
+
+W = 256
+GRIDS = (0, 1, 7)
+
+
+@pytest.fixture(scope="module")
+def torch_dev():
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    return torch
+
+
+@pytest.fixture(scope="module")
+def cref():
+    return CRef()
+
+
+def _inputs(m, D, H=40, seed=0):
+    """name -> (L, R): the random pair and the two carry stressors."""
+    L, R, _ = stereo_pair(H, W, m, D, seed=1000 + 7 * D + m + seed)
+    white = np.full((H, W), 255, np.uint8)
+    x = np.arange(W)[None, :]
+    y = np.arange(H)[:, None]
+    cols = np.broadcast_to(((x & 1) * 255).astype(np.uint8), (H, W)).copy()  # columns 0, 255, 0, ...
+    rows = (((x + y) & 1) * 255).astype(np.uint8)                            # rows alternate as well
+    return {"random": (L, R), "carry_cols": (white, cols), "carry_rows": (white, rows)}
+
+
+def _check(got, want, what):
+    bad = np.argwhere(got != want)
+    assert bad.size == 0, (f"{what}: {len(bad)} of {got.size} pixels differ, first {bad[:4].tolist()}: "
+                           f"got {got[tuple(bad[0])]} want {want[tuple(bad[0])]}")
+
+
+def _check_both(fixed, flt, want, what):
+    """int16 x16 map and float map (x16 / 16) against the oracle's x16 map."""
+    _check(fixed.cpu().numpy(), want, what + " fixed")
+    _check(flt.cpu().numpy(), want.astype(np.float32) / np.float32(16), what + " float")
+
+
+def _left(torch, pairs, wants, what, grids=GRIDS, **kw):
+    """One matcher per grid, every input through it, both outputs checked."""
+    from depthestimation_amd.matcher import HipBlockMatcher
+    for g in grids:
+        mt = HipBlockMatcher(grid_blocks=g, **kw)
+        try:
+            for name, (L, R) in pairs.items():
+                H = L.shape[0]
+                fx = torch.empty((H, W), dtype=torch.int16, device="cuda")
+                fl = torch.empty((H, W), dtype=torch.float32, device="cuda")
+                mt.compute_device(torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda(), out_fixed=fx, out_float=fl)
+                torch.cuda.synchronize()
+                _check_both(fx, fl, wants[name], f"{what} grid_blocks={g} input={name}")
+        finally:
+            mt.close()
+
+
+PLAIN = dict(uniqueness_ratio=0, disp12_max_diff=-1)
+LRBM = dict(uniqueness_ratio=10, disp12_max_diff=1, lr_form="bm")
+
+
+def _cref_all(cref, pairs, m, D, bs, cost, u, lr):
+    return {n: cref(L, R, m, D, bs, cost, u, lr, True)["fixed"] for n, (L, R) in pairs.items()}
+
+
+@pytest.mark.parametrize("H", [1, 2, 9, 10, 40])
+def test_segment_ends(torch_dev, cref, H):
+    """R = 4, D = 128: segments that end (and start) on every row, frames shorter than the window."""
+    m, D, bs = 0, 128, 9
+    pairs = _inputs(m, D, H)
+    grids = GRIDS + ((W // 32) * H,)
+    base = dict(min_disp=m, num_disp=D, block_size=bs, cost="sad")
+    _left(torch_dev, pairs, _cref_all(cref, pairs, m, D, bs, "sad", 0, -1), f"H={H} left", grids, **PLAIN, **base)
+    _left(torch_dev, pairs, _cref_all(cref, pairs, m, D, bs, "sad", 10, 1), f"H={H} lr bm", grids, **LRBM, **base)
+
+
+@pytest.mark.parametrize("cost,bs,D", [("sad", 9, 131), ("sad", 9, 192), ("ssd", 5, 128), ("ssd", 11, 128),
+                                       ("ssd", 5, 256), ("ssd", 11, 256), ("ssd", 13, 128)])
+def test_staging_parity_multiwave(torch_dev, cref, cost, bs, D):
+    m = 0
+    pairs = _inputs(m, D)
+    base = dict(min_disp=m, num_disp=D, block_size=bs, cost=cost)
+    _left(torch_dev, pairs, _cref_all(cref, pairs, m, D, bs, cost, 0, -1), "left", **PLAIN, **base)
+    _left(torch_dev, pairs, _cref_all(cref, pairs, m, D, bs, cost, 10, 1), "lr bm", **LRBM, **base)
+
+
+@pytest.mark.parametrize("bs,m", [(5, 0), (9, 0), (9, 5), (9, -3), (15, 0)])
+def test_all_sides(torch_dev, cref, bs, m):
+    torch = torch_dev
+    from depthestimation_amd.matcher import HipBlockMatcher
+    D = 128
+    pairs = _inputs(m, D)
+    base = dict(min_disp=m, num_disp=D, block_size=bs, cost="sad")
+    vols = {n: cost_volume(L, R, m, D, bs, "sad") for n, (L, R) in pairs.items()}
+    _left(torch, pairs, _cref_all(cref, pairs, m, D, bs, "sad", 0, -1), "left", **PLAIN, **base)
+    lr = _cref_all(cref, pairs, m, D, bs, "sad", 10, 1)
+    _left(torch, pairs, lr, "lr bm", **LRBM, **base)
+    _left(torch, pairs, {n: wta_sgbm(vols[n], m, 10, 1, True)["fixed"] for n in pairs}, "lr sgbm",
+          uniqueness_ratio=10, disp12_max_diff=1, lr_form="sgbm", path="fused", **base)
+    _left(torch, pairs, lr, "volume", path="volume", uniqueness_ratio=10, disp12_max_diff=1, **base)
+    for g in GRIDS:
+        mt = HipBlockMatcher(grid_blocks=g, **base)
+        try:
+            for name, (L, R) in pairs.items():
+                out = torch.empty(L.shape, dtype=torch.int16, device="cuda")
+                mt.right_map_device(torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda(), out)
+                torch.cuda.synchronize()
+                _check(out.cpu().numpy().astype(np.int32), right_argmin(vols[name], m),
+                       f"right map grid_blocks={g} input={name}")
+        finally:
+            mt.close()
+
+
+@pytest.mark.parametrize("pad", [0, 24])
+def test_two_frames_and_padded_rows(torch_dev, cref, pad):
+    """compute_batch_device with two different frames (H = 19: with 7 blocks a block's rows cross
+    the frame boundary), contiguous and with rows padded to W + 24; compute_device with padded rows."""
+    torch = torch_dev
+    from depthestimation_amd.matcher import HipBlockMatcher
+    m, D, bs, H = 0, 128, 9, 19
+    fr = [_inputs(m, D, H, seed=s)["random"] for s in (0, 1)]
+    bufL = torch.zeros((2, H, W + pad), dtype=torch.uint8, device="cuda")
+    bufR = torch.zeros((2, H, W + pad), dtype=torch.uint8, device="cuda")
+    dL, dR = bufL[:, :, :W], bufR[:, :, :W]
+    for i, (L, R) in enumerate(fr):
+        dL[i].copy_(torch.from_numpy(L))
+        dR[i].copy_(torch.from_numpy(R))
+    base = dict(min_disp=m, num_disp=D, block_size=bs, cost="sad")
+    for what, kw, u, lr in (("left", PLAIN, 0, -1), ("lr bm", LRBM, 10, 1)):
+        wants = [cref(L, R, m, D, bs, "sad", u, lr, True)["fixed"] for L, R in fr]
+        for g in GRIDS:
+            mt = HipBlockMatcher(grid_blocks=g, **kw, **base)
+            try:
+                fx = torch.empty((2, H, W), dtype=torch.int16, device="cuda")
+                fl = torch.empty((2, H, W), dtype=torch.float32, device="cuda")
+                mt.compute_batch_device(dL, dR, out_fixed=fx, out_float=fl)
+                torch.cuda.synchronize()
+                for i in range(2):
+                    _check_both(fx[i], fl[i], wants[i], f"batch {what} pad={pad} grid_blocks={g} frame={i}")
+                fx1 = torch.empty((H, W), dtype=torch.int16, device="cuda")
+                fl1 = torch.empty((H, W), dtype=torch.float32, device="cuda")
+                mt.compute_device(dL[1], dR[1], out_fixed=fx1, out_float=fl1)
+                torch.cuda.synchronize()
+                _check_both(fx1, fl1, wants[1], f"single {what} pad={pad} grid_blocks={g}")
+            finally:
+                mt.close()
+
+
+def test_three_in_flight(torch_dev, cref):
+    """Three in_flight handles on three streams, two rounds, each with its own frame and oracle."""
+    torch = torch_dev
+    from depthestimation_amd.matcher import HipBlockMatcher
+    m, D, bs, H = 0, 128, 9, 40
+    fr = [_inputs(m, D, H, seed=s)["random"] for s in (0, 1, 2)]
+    wants = [cref(L, R, m, D, bs, "sad", 0, -1, True)["fixed"] for L, R in fr]
+    dev = [(torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda()) for L, R in fr]
+    handles = [HipBlockMatcher(in_flight=True, min_disp=m, num_disp=D, block_size=bs, cost="sad", **PLAIN) for _ in range(3)]
+    streams = [torch.cuda.Stream() for _ in range(3)]
+    fx = [torch.empty((H, W), dtype=torch.int16, device="cuda") for _ in range(6)]
+    fl = [torch.empty((H, W), dtype=torch.float32, device="cuda") for _ in range(6)]
+    torch.cuda.synchronize()
+    try:
+        for i in range(6):
+            handles[i % 3].compute_device(*dev[i % 3], out_fixed=fx[i], out_float=fl[i], stream=streams[i % 3])
+        torch.cuda.synchronize()
+        for i in range(6):
+            _check_both(fx[i], fl[i], wants[i % 3], f"in_flight handle {i % 3} call {i // 3}")
+    finally:
+        for h in handles:
+            h.close()

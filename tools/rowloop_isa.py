@@ -1,0 +1,161 @@
+"""Row-loop ISA report of the fused block-matching pass (csrc/dsx_bm.hip).
+
+Cross-compiles one radius unit with -S (as tools/valu_roofline.py does) and prints, for every row
+loop of an instantiation (the unaligned-dword copy and the clamped-byte copy of bm2_segment):
+
+  * the VALU instruction count;
+  * counts of ds_read2_b64, ds_read_b64, v_mad_u64_u32 and s_waitcnt vmcnt(..);
+  * where each vmcnt wait sits in the step, counted from the step's first global load: how many
+    of the loop's global loads and global_store_* / global_atomic_* precede it (a wait behind all
+    of the stores is in the step's tail or at the next step's header);
+  * the kernel's VGPRs, scratch bytes and LDS bytes per block (Geo in dsx_bm.hip, restated here).
+
+It reports; it gates nothing.
+
+usage:
+  python tools/rowloop_isa.py [c2 c2r c4 c5 c1 c3 ...] [--src <dsx_bm.hip>] [--tag <text>]
+"""
+from __future__ import annotations
+
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from valu_roofline import BENCH_KERNELS, ROOT, blocks, function_body, kernel_label, row_loops, symbol  # noqa: E402
+
+ORDER = ["c2", "c2r", "c4", "c5", "c1", "c3"]
+
+
+def rnd16(v):
+    return (v + 15) & ~15
+
+
+def lds_bytes(r, ssd, nw, side):
+    """Geo<R, SSD, NW>::SMEM plus the SAD LR pass's exit region (launch_bm2_side)."""
+    tx, nc, kd = 32, 32 + 2 * r, (1 if ssd else 2)
+    dp = nw * 64 * kd
+    pitch = dp * (4 if ssd else 2) + 16
+    slot = rnd16((nc + dp) * 4 + 16) + rnd16(4 * (nc + 8))
+    smem = max(4 * slot + tx * pitch, (2 * r + 1) * slot)
+    return smem + (128 * nw if side == 3 and not ssd else 0)
+
+
+def meta(asm, sym):
+    m = re.search(r"\.amdhsa_kernel " + re.escape(sym) + r"\n(.*?)\.end_amdhsa_kernel", asm, re.S)
+    d = {k: int(v) for k, v in re.findall(r"\.amdhsa_(\w+) (\d+)", m.group(1))} if m else {}
+    return d.get("next_free_vgpr"), d.get("private_segment_fixed_size"), d.get("accum_offset")
+
+
+def lines_of(body):
+    """[(block label, op, operands)] in layout order."""
+    out, lab = [], "entry"
+    for line in body.split("\n"):
+        if line.startswith(".LBB"):
+            lab = line.split(":")[0]
+        elif line.startswith("\t"):
+            t = line.strip()
+            if t and not t.startswith((".", ";")):
+                p = t.split(None, 1)
+                out.append((lab, p[0], p[1] if len(p) > 1 else ""))
+    return out
+
+
+def report(asm, name, out):
+    r, ssd, nw, side, abs_ = BENCH_KERNELS[name]
+    sym = symbol(r, ssd, nw, side, abs_)
+    body = function_body(asm, sym)
+    bl = blocks(body)
+    loops, nvalu = row_loops(bl)
+    vg, scratch, acc = meta(asm, sym)
+    out(f"{name} {kernel_label(r, ssd, nw, side, abs_)}: VGPRs {vg} (accum offset {acc}), scratch {scratch} B, "
+        f"LDS {lds_bytes(r, ssd, nw, side)} B per block")
+    ln = lines_of(body)
+    for i, j in loops:
+        labs = {bl[k][0] for k in range(i, j + 1)}
+        ops = [(lab, op, arg) for lab, op, arg in ln if lab in labs]
+        cnt = lambda p: sum(1 for _, op, _ in ops if op.startswith(p))  # noqa: E731
+        out(f"  loop {bl[i][0]} .. {bl[j][0]}: VALU {nvalu((i, j))}, ds_read2_b64 {cnt('ds_read2_b64')}, "
+            f"ds_read_b64 {cnt('ds_read_b64')}, v_mad_u64_u32 {cnt('v_mad_u64_u32')}, "
+            f"global loads {cnt('global_load')}, global stores/atomics {cnt('global_store') + cnt('global_atomic')}")
+        # The compiler lays the blocks of a step out of program order (the column update and the
+        # box phase sit behind the stores in the listing), so positions are taken from the control
+        # flow: op k leads to op k + 1 (unless it is s_branch) and to its branch target.  The step
+        # is cut at its global loads (the prefetch).  A wait "follows a store" when a store reaches
+        # it without crossing a load - tail of the step or header of the next one - and is "at the
+        # header" when the loop's header block reaches it before any load or LDS operation.
+        at = {}
+        for k, (lab, _, _) in enumerate(ops):
+            at.setdefault(lab, k)
+        loads = {k for k, (_, op, _) in enumerate(ops) if op.startswith("global_load")}
+        lds = {k for k, (_, op, _) in enumerate(ops) if op.startswith("ds_")}
+
+        def reach(starts, cut):
+            seen, todo = set(), list(starts)
+            while todo:
+                k = todo.pop()
+                if k in seen or k >= len(ops):
+                    continue
+                seen.add(k)
+                if k in cut:
+                    continue
+                _, op, arg = ops[k]
+                if op.startswith(("s_cbranch", "s_branch")):
+                    t = re.search(r"(\.LBB\d+_\d+)", arg)
+                    if t and t.group(1) in at:
+                        todo.append(at[t.group(1)])
+                if op != "s_branch" and k + 1 < len(ops) and (ops[k + 1][0] == ops[k][0] or ops[k + 1][0] in at):
+                    todo.append(k + 1)
+            return seen
+
+        hdr = re.findall(r"in Loop: Header=(BB\d+_\d+) Depth=2", "\n".join(
+            b for b in re.split(r"\n(?=\.LBB\d+_\d+:)", body) if b.split(":")[0] in labs))
+        head = ".L" + max(set(hdr), key=hdr.count) if hdr else ops[0][0]
+        after_store = reach([k + 1 for k, (_, op, _) in enumerate(ops) if op.startswith(("global_store", "global_atomic"))], loads)
+        at_header = reach([at[head]], loads | lds) if head in at else set()
+        waits = []
+        for k, (lab, op, arg) in enumerate(ops):
+            if op == "s_waitcnt" and "vmcnt" in arg:
+                v = re.search(r"vmcnt\((\d+)\)", arg).group(1)
+                where = [w for w, c in (("at the loop header", k in at_header), ("follows a store of the step", k in after_store)) if c]
+                waits.append(f"    vmcnt({v}) in {lab}: {', '.join(where) or 'between the prefetch and the stores'}")
+        out(f"    s_waitcnt vmcnt: {len(waits)}")
+        for w in waits:
+            out(w)
+
+
+def main(argv):
+    src = os.path.join(ROOT, "depthestimation_amd", "csrc", "dsx_bm.hip")
+    tag = None
+    names = []
+    it = iter(argv)
+    for a in it:
+        if a == "--src":
+            src = next(it)
+        elif a == "--tag":
+            tag = next(it)
+        else:
+            names.append(a)
+    names = names or ORDER
+    out = print
+    if tag:
+        out(f"== {tag} ==")
+    tmp = tempfile.mkdtemp(prefix="dsx_rowloop_")
+    asm = {}
+    procs = {}
+    for r in sorted({BENCH_KERNELS[n][0] for n in names}):
+        procs[r] = subprocess.Popen(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", f"-DDSX_RADIUS={r}",
+                                     "-I", os.path.dirname(src), "--cuda-device-only", "-S", "-o",
+                                     os.path.join(tmp, f"r{r}.s"), src], stderr=subprocess.DEVNULL)
+    for r, p in procs.items():
+        if p.wait() != 0:
+            raise SystemExit(f"hipcc failed for radius {r}")
+        asm[r] = open(os.path.join(tmp, f"r{r}.s")).read()
+    for n in names:
+        report(asm[BENCH_KERNELS[n][0]], n, out)
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

@@ -55,7 +55,7 @@ if ext.size >= 12 * 65536:
     ps = ext[4 * 65536:].reshape(-1, 8)[: len(t)]
     if ps[:, 7].sum() > 0:
         steps = ps[:, 7].astype(np.float64)
-        names = ["update", "prefetch-issue", "horizontal", "barrier1", "epilogue", "store-row", "barrier2"]
+        names = ["update", "prefetch-issue", "horizontal", "barrier1", "store-row", "epilogue", "barrier2"]
         tot = ps[:, :7].astype(np.float64).sum(0) / steps.sum()
         print("cycles per row-step (s_memtime):", {n: round(v, 1) for n, v in zip(names, tot)}, "sum", round(tot.sum(), 1))
 # duration by strip (block b owns strip b * NS / NG in the one-strip-per-block regime)
