@@ -37,6 +37,8 @@ EXPORTS = (
     "dsx_fill_holes_status_ws", "dsx_fill_holes_status_handle", "dsx_fill_holes_release", "dsx_shutdown",
     "dsx_kernel_times", "dsx_reset_times", "dsx_workspace_bytes", "dsx_destroy", "dsx_last_error",
     "dsx_comm_init_all", "dsx_comm_size", "dsx_bcast", "dsx_comm_destroy",
+    "dsx_fill_nearest_footprint", "dsx_fill_nearest_workspace_bytes", "dsx_fill_nearest_device",
+    "dsx_postprocess_device",
 )
 
 
@@ -70,6 +72,9 @@ class DsxParams(ctypes.Structure):
 
 
 POST_MODE = {"fast": 1, "full": 2}  # DSX_POST_* (include/dsx.h)
+FILL_METHOD = {"inpaint": 0, "nearest": 1}  # DSX_FILL_* (fill_holes' method names, postprocess.py:72-118)
+NEAREST_PATH = {"auto": 0, "fused": 1, "stepwise": 2}  # DSX_NEAREST_*
+NEAREST_FUSED_MAX = 5  # DSX_NEAREST_FUSED_MAX
 
 
 class DsxPostParams(ctypes.Structure):
@@ -91,7 +96,8 @@ class DsxPostParams(ctypes.Structure):
         ("has_max_depth", ctypes.c_int32),
         ("fill_spin_limit", ctypes.c_uint32),
         ("fill_steps", ctypes.c_int32),
-        ("reserved", ctypes.c_int32 * 3),
+        ("fill_method", ctypes.c_int32),
+        ("reserved", ctypes.c_int32 * 2),
     ]
 
 
@@ -133,6 +139,11 @@ def _bind(lib):
                                                            ctypes.c_double, i32, vp, ctypes.c_size_t, vp]),
         "dsx_fill_holes_workspace_bytes": (ctypes.c_size_t, [i32, i32]),
         "dsx_fill_holes_device": (ctypes.c_int, [vp, i32, i32, i64, i32, vp, vp, ctypes.c_size_t, vp]),
+        "dsx_fill_nearest_footprint": (ctypes.c_int, [i32, ctypes.POINTER(ctypes.c_int32), i32]),
+        "dsx_fill_nearest_workspace_bytes": (ctypes.c_size_t, [i32, i32]),
+        "dsx_fill_nearest_device": (ctypes.c_int, [vp, i32, i32, i64, i32, vp, vp, ctypes.c_size_t, i32, vp]),
+        "dsx_postprocess_device": (ctypes.c_int, [vp, i32, i32, i64, i32, ctypes.POINTER(DsxPostParams), vp, vp, vp,
+                                                   ctypes.c_size_t, vp]),
         "dsx_rectify_device": (ctypes.c_int, [vp, i32, i32, i64, i32, vp, vp, i32, i32, vp, vp]),
         "dsx_postprocess_fast_device": (ctypes.c_int, [vp, i32, i32, i64, i32, vp, vp, ctypes.c_double,
                                                         ctypes.c_double, ctypes.c_double, ctypes.c_double,

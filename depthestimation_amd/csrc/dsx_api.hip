@@ -733,6 +733,10 @@ namespace dsx {
 int set_error(int code, const std::string &msg) { return fail(code, msg); }
 }  // namespace dsx
 
+static_assert(dsx::kFillInpaint == DSX_FILL_INPAINT && dsx::kFillNearest == DSX_FILL_NEAREST, "fill methods");
+static_assert(dsx::kNearestFused == DSX_NEAREST_FUSED && dsx::kNearestStep == DSX_NEAREST_STEPWISE &&
+                  dsx::kNearestFusedMaxK == DSX_NEAREST_FUSED_MAX, "nearest paths");
+
 extern "C" {
 
 int dsx_version(void) { return DSX_VERSION; }
@@ -866,14 +870,20 @@ int dsx_postprocess_full_device(const void *d_disp, int32_t H, int32_t W, int64_
                                           d_workspace, workspace_bytes, hip_stream);
 }
 
-int dsx_postprocess_full_ex_device(const void *d_disp, int32_t H, int32_t W, int64_t in_pitch, int32_t crop,
-                                   int32_t max_speckle_size, double max_diff, int32_t apply_outlier_removal,
-                                   double outlier_threshold, int32_t outlier_kernel, int32_t fill_radius,
-                                   void *d_out_disp, void *d_out_depth, double focal_length, double baseline,
-                                   double doffs, double eps, double max_depth, int32_t has_max_depth,
-                                   void *d_workspace, size_t workspace_bytes, void *hip_stream) {
+namespace {
+// the stand-alone chain behind dsx_postprocess_full_ex_device and dsx_postprocess_device
+int post_full_standalone(const void *d_disp, int32_t H, int32_t W, int64_t in_pitch, int32_t crop,
+                         int32_t max_speckle_size, double max_diff, int32_t apply_outlier_removal,
+                         double outlier_threshold, int32_t outlier_kernel, int32_t fill_radius, int32_t fill_method,
+                         const dsx::InpaintOpts &fill_opts, void *d_out_disp, void *d_out_depth, double focal_length,
+                         double baseline, double doffs, double eps, double max_depth, int32_t has_max_depth,
+                         void *d_workspace, size_t workspace_bytes, void *hip_stream) {
     g_err.clear();
     if (fill_radius < 0) return fail(DSX_EINVAL, "fill_radius must be >= 0");
+    if (fill_method != DSX_FILL_INPAINT && fill_method != DSX_FILL_NEAREST)
+        return fail(DSX_EINVAL, "fill_method must be DSX_FILL_INPAINT or DSX_FILL_NEAREST");
+    if (fill_method == DSX_FILL_NEAREST && fill_radius > dsx::kNearestMaxK)
+        return fail(DSX_EINVAL, "fill_method 'nearest': kernel_size (fill_radius) must be in [0, 31]");
     if (!d_disp) return fail(DSX_EINVAL, "d_disp is NULL");
     if (H <= 0 || W <= 0 || in_pitch < W || crop < 0) return fail(DSX_EINVAL, "bad shape / pitch / crop");
     if (outlier_kernel < 1 || (outlier_kernel & 1) == 0) return fail(DSX_EINVAL, "outlier_kernel must be odd");
@@ -881,7 +891,7 @@ int dsx_postprocess_full_ex_device(const void *d_disp, int32_t H, int32_t W, int
     if (!d_workspace || workspace_bytes < dsx::post_full_workspace(H, W, crop))
         return fail(DSX_EINVAL, "workspace too small (dsx_postprocess_workspace_bytes)");
     if ((int64_t)H * (W - crop) > 0x7FFFFFFF) return fail(DSX_EINVAL, "image too large for int32 labels");
-    if (fill_radius > 0) {
+    if (fill_radius > 0 && fill_method == DSX_FILL_INPAINT) {
         int rc = check_fill_shape(H, W - crop);
         if (!rc) rc = sticky_inpaint_timeout(d_workspace);
         if (rc) return rc;
@@ -905,7 +915,74 @@ int dsx_postprocess_full_ex_device(const void *d_disp, int32_t H, int32_t W, int
     a.max_depth = (float)max_depth;
     a.has_max = has_max_depth ? 1 : 0;
     a.fill_radius = fill_radius;
+    a.fill_method = fill_method;
+    a.fill_opts = fill_opts;
     DSX_HIP(dsx::launch_post_full(a, d_workspace, static_cast<hipStream_t>(hip_stream)));
+    return DSX_OK;
+}
+}  // namespace
+
+int dsx_postprocess_full_ex_device(const void *d_disp, int32_t H, int32_t W, int64_t in_pitch, int32_t crop,
+                                   int32_t max_speckle_size, double max_diff, int32_t apply_outlier_removal,
+                                   double outlier_threshold, int32_t outlier_kernel, int32_t fill_radius,
+                                   void *d_out_disp, void *d_out_depth, double focal_length, double baseline,
+                                   double doffs, double eps, double max_depth, int32_t has_max_depth,
+                                   void *d_workspace, size_t workspace_bytes, void *hip_stream) {
+    return post_full_standalone(d_disp, H, W, in_pitch, crop, max_speckle_size, max_diff, apply_outlier_removal,
+                                outlier_threshold, outlier_kernel, fill_radius, DSX_FILL_INPAINT, dsx::InpaintOpts{},
+                                d_out_disp, d_out_depth, focal_length, baseline, doffs, eps, max_depth, has_max_depth,
+                                d_workspace, workspace_bytes, hip_stream);
+}
+
+int dsx_postprocess_device(const void *d_disp, int32_t H, int32_t W, int64_t in_pitch, int32_t crop,
+                           const dsx_post_params *pp, void *d_out_disp, void *d_out_depth, void *d_workspace,
+                           size_t workspace_bytes, void *hip_stream) {
+    g_err.clear();
+    if (!pp) return fail(DSX_EINVAL, "NULL post parameters");
+    if (pp->mode != DSX_POST_FULL) return fail(DSX_EINVAL, "dsx_postprocess_device runs mode DSX_POST_FULL");
+    dsx::InpaintOpts fo;
+    fo.spin_limit = pp->fill_spin_limit;
+    fo.steps = pp->fill_steps == 0 ? -1 : std::max(0, (int)pp->fill_steps);
+    return post_full_standalone(d_disp, H, W, in_pitch, crop, pp->max_speckle_size, pp->max_diff,
+                                pp->apply_outlier_removal, pp->outlier_threshold, pp->outlier_kernel, pp->fill_radius,
+                                pp->fill_method, fo, d_out_disp, pp->has_depth ? d_out_depth : nullptr,
+                                pp->focal_length, pp->baseline, pp->doffs, pp->eps, pp->max_depth, pp->has_max_depth,
+                                d_workspace, workspace_bytes, hip_stream);
+}
+
+size_t dsx_fill_nearest_workspace_bytes(int32_t H, int32_t W) {
+    if (H <= 0 || W <= 0) return 0;
+    return dsx::nearest_workspace(H, W);
+}
+
+int dsx_fill_nearest_footprint(int32_t kernel_size, int32_t *halfwidths, int32_t cap) {
+    g_err.clear();
+    if (kernel_size < 0 || kernel_size > dsx::kNearestMaxK) return fail(DSX_EINVAL, "kernel_size must be in [0, 31]");
+    if (!halfwidths || cap < 2 * (kernel_size / 2) + 1)
+        return fail(DSX_EINVAL, "halfwidths needs 2 * (kernel_size / 2) + 1 entries");
+    return dsx::nearest_footprint(kernel_size, halfwidths, cap);
+}
+
+int dsx_fill_nearest_device(const void *d_disp, int32_t H, int32_t W, int64_t in_pitch, int32_t kernel_size,
+                            void *d_out, void *d_workspace, size_t workspace_bytes, int32_t path, void *hip_stream) {
+    g_err.clear();
+    if (!d_disp || !d_out) return fail(DSX_EINVAL, "NULL input or output");
+    if (d_out == d_disp) return fail(DSX_EINVAL, "d_out must not be d_disp (every iteration reads the previous one)");
+    if (H <= 0 || W <= 0 || in_pitch < W) return fail(DSX_EINVAL, "bad shape / pitch");
+    if (kernel_size < 0 || kernel_size > dsx::kNearestMaxK) return fail(DSX_EINVAL, "kernel_size must be in [0, 31]");
+    if (path != DSX_NEAREST_AUTO && path != DSX_NEAREST_FUSED && path != DSX_NEAREST_STEPWISE)
+        return fail(DSX_EINVAL, "path must be DSX_NEAREST_AUTO, DSX_NEAREST_FUSED or DSX_NEAREST_STEPWISE");
+    if (path == DSX_NEAREST_FUSED && kernel_size > DSX_NEAREST_FUSED_MAX)
+        return fail(DSX_EINVAL, "the fused path covers kernel_size <= DSX_NEAREST_FUSED_MAX");
+    if ((int64_t)H > 4 * 65535) return fail(DSX_EINVAL, "image too tall (H > 262140)");
+    if (path == DSX_NEAREST_AUTO) path = kernel_size <= DSX_NEAREST_FUSED_MAX ? DSX_NEAREST_FUSED : DSX_NEAREST_STEPWISE;
+    if (path == DSX_NEAREST_STEPWISE && kernel_size >= 2 &&
+        (!d_workspace || workspace_bytes < dsx::nearest_workspace(H, W)))
+        return fail(DSX_EINVAL, "workspace too small (dsx_fill_nearest_workspace_bytes)");
+    DSX_HIP(dsx::launch_nearest(static_cast<const float *>(d_disp), in_pitch, H, W, kernel_size,
+                                static_cast<float *>(d_out), static_cast<float *>(d_workspace),
+                                path == DSX_NEAREST_FUSED ? dsx::kNearestFused : dsx::kNearestStep,
+                                static_cast<hipStream_t>(hip_stream)));
     return DSX_OK;
 }
 
@@ -1078,6 +1155,10 @@ int dsx_process_pair_device(dsx_handle *h, const void *dL, const void *dR, int32
     if (pp->mode == DSX_POST_FULL) {
         if (pp->outlier_kernel < 1 || (pp->outlier_kernel & 1) == 0) return fail(DSX_EINVAL, "outlier_kernel must be odd");
         if (pp->fill_radius < 0) return fail(DSX_EINVAL, "fill_radius must be >= 0");
+        if (pp->fill_method != DSX_FILL_INPAINT && pp->fill_method != DSX_FILL_NEAREST)
+            return fail(DSX_EINVAL, "fill_method must be DSX_FILL_INPAINT or DSX_FILL_NEAREST");
+        if (pp->fill_method == DSX_FILL_NEAREST && pp->fill_radius > dsx::kNearestMaxK)
+            return fail(DSX_EINVAL, "fill_method 'nearest': kernel_size (fill_radius) must be in [0, 31]");
     }
     if (h->p.float_mode != DSX_FLOAT_FIXED)
         return fail(DSX_EINVAL, "process_pair needs float_mode DSX_FLOAT_FIXED (stereo_core.py:232: fixed / 16)");
@@ -1085,7 +1166,7 @@ int dsx_process_pair_device(dsx_handle *h, const void *dL, const void *dR, int32
     const int Wc = W - crop;
     const bool depth = pp->has_depth != 0;
     if (Wc <= 0 || (!d_out_disp && !(depth && d_out_depth))) return DSX_OK;  // disp[:, num_disp:] is empty
-    if (pp->mode == DSX_POST_FULL && pp->fill_radius > 0) {
+    if (pp->mode == DSX_POST_FULL && pp->fill_radius > 0 && pp->fill_method == DSX_FILL_INPAINT) {
         rc = check_fill_shape(H, Wc);
         if (!rc) rc = sticky_inpaint_timeout(h);
         if (rc) return rc;
@@ -1152,6 +1233,7 @@ int dsx_process_pair_device(dsx_handle *h, const void *dL, const void *dR, int32
         a.max_depth = (float)pp->max_depth;
         a.has_max = pp->has_max_depth ? 1 : 0;
         a.fill_radius = pp->fill_radius;
+        a.fill_method = pp->fill_method;
         a.fill_opts.status_key = h;  // the handle's own timeout flag and step history
         a.fill_opts.spin_limit = pp->fill_spin_limit;
         a.fill_opts.steps = pp->fill_steps == 0 ? -1 : std::max(0, (int)pp->fill_steps);

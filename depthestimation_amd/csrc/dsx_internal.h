@@ -158,7 +158,8 @@ struct PostFullArgs {
     float *out_disp, *out_depth;
     float fB, doffs, eps, max_depth;
     int has_max;
-    int fill_radius;  // > 0: Telea hole filling (radius) between the outlier removal and the median
+    int fill_radius;  // > 0: hole filling between the outlier removal and the median: Telea (radius), or
+    int fill_method;  // with DSX_FILL_NEAREST the iterated dilation (fill_radius = kernel_size)
     InpaintOpts fill_opts;  // status key (nullptr: the post-processing workspace), spin bound
     int tail_t1;      // post_tail writes the outlier-cleaned map to t1 instead of the median (set internally)
     // workspace views (set by launch_post_full)
@@ -217,6 +218,20 @@ int inpaint_take_timeout_any();
 void inpaint_forget(const void *key);
 void inpaint_forget_all();
 bool inpaint_has_words();
+
+// Hole filling by iterated dilation (dsx_nearest.hip): fill_holes(method='nearest') on d <= 0, k masked
+// dilations with the ellipse footprint of radius k / 2.  Stateless, block barriers only.
+constexpr int kNearestMaxK = 31;      // kernel_size bound: at most 31 footprint rows
+constexpr int kNearestFusedMaxK = 5;  // the fused (all iterations in LDS) path's bound
+constexpr int kNearestFused = 1, kNearestStep = 2;
+constexpr int kFillInpaint = 0, kFillNearest = 1;  // PostFullArgs.fill_method (DSX_FILL_* of dsx.h)
+// per-row half-widths of the footprint (hw[dy + r], -1: empty row); returns the row count 2 (k / 2) + 1,
+// or -1 for k outside [0, kNearestMaxK] / cap too small.  Host only: the one C home of the ellipse rule.
+int nearest_footprint(int k, int32_t *hw, int cap);
+size_t nearest_workspace(int H, int W);  // the stepwise path's second buffer (k >= 2)
+// path: kNearestFused (k <= kNearestFusedMaxK, ws unused) or kNearestStep (ws needed for k >= 2)
+hipError_t launch_nearest(const float *in, int64_t pitch, int H, int W, int k, float *out, float *ws, int path,
+                          hipStream_t st);
 
 // Birchfield-Tomasi block costs into K1's volume layout (dsx_bt.hip, oracle/bt_cost.py)
 struct BtArgs {

@@ -1145,10 +1145,19 @@ hipError_t launch_post_full(PostFullArgs a, void *ws, hipStream_t st, LaunchHook
     if (fill) {
         // fill_holes (postprocess.py:160-166) on the cleaned map: t1 (or t0) -> t0, then the median
         float *dst = med_in == a.t0 ? a.t1 : a.t0;
-        mark("fill_holes");
-        InpaintOpts fo = a.fill_opts;
-        if (!fo.status_key) fo.status_key = ws;
-        hipError_t e = launch_inpaint(med_in, Wc, a.H, Wc, a.fill_radius, dst, inpaint_ws, st, fo);
+        hipError_t e;
+        if (a.fill_method == kFillNearest) {
+            // 'nearest': fill_radius is the kernel_size; stateless, no status key.  The stepwise path
+            // (kernel_size past the fused bound) alternates with the idle inpaint area.
+            mark("fill_nearest");
+            const int path = a.fill_radius <= kNearestFusedMaxK ? kNearestFused : kNearestStep;
+            e = launch_nearest(med_in, Wc, a.H, Wc, a.fill_radius, dst, reinterpret_cast<float *>(inpaint_ws), path, st);
+        } else {
+            mark("fill_holes");
+            InpaintOpts fo = a.fill_opts;
+            if (!fo.status_key) fo.status_key = ws;
+            e = launch_inpaint(med_in, Wc, a.H, Wc, a.fill_radius, dst, inpaint_ws, st, fo);
+        }
         if (hook) hook->after(st);
         if (e != hipSuccess) return e;
         med_in = dst;

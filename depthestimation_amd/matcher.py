@@ -33,6 +33,13 @@ def _device_index(t):
     return i if i >= 0 else 0
 
 
+def _fill_method(name) -> int:
+    """DSX_FILL_* of fill_holes' method name (postprocess.py:72-118); ValueError for any other."""
+    if name not in _dsx.FILL_METHOD:
+        raise ValueError(f"fill method must be one of {list(_dsx.FILL_METHOD)}, got {name!r}")
+    return _dsx.FILL_METHOD[name]
+
+
 _DTYPES = {}
 
 
@@ -218,11 +225,12 @@ class HipBlockMatcher:
     def process_pair_device(self, left, right, fast_mode=False, max_speckle_size=100, max_diff=1.0,
                             apply_outlier_removal=True, outlier_threshold=2.5, outlier_kernel=5, fill_radius=0,
                             focal_length=None, baseline=None, doffs=0.0, eps=1e-6, max_depth=None, out_disp=None,
-                            out_depth=None, stream=None, fill_spin_limit=0, fill_steps=0):
+                            out_depth=None, stream=None, fill_spin_limit=0, fill_steps=0, fill_method="inpaint"):
         """StereoCore._process_pair (stereo_core.py:162-200) in ONE C-ABI call
         (dsx_process_pair_device): matcher -> crop [:, num_disp:] -> fast-mode median or
-        postprocess_disparity (speckles, outliers, Telea hole filling when ``fill_radius`` > 0,
-        median) -> depth when focal length and baseline are given.  ``left``/``right``: uint8 HIP
+        postprocess_disparity (speckles, outliers, hole filling when ``fill_radius`` > 0: Telea with
+        ``fill_method`` 'inpaint', the iterated dilation with 'nearest', where ``fill_radius`` is the
+        kernel_size; median) -> depth when focal length and baseline are given.  ``left``/``right``: uint8 HIP
         tensors H x W (unit column stride, equal row strides).  Returns float32 HIP tensors
         (disparity H x (W - num_disp), depth or None); asynchronous on ``stream``."""
         import torch
@@ -259,6 +267,7 @@ class HipBlockMatcher:
         pp.has_max_depth = int(max_depth is not None)
         pp.fill_spin_limit = int(fill_spin_limit)
         pp.fill_steps = int(fill_steps)
+        pp.fill_method = _fill_method(fill_method)
         sptr = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
         rc = _dsx.lib().dsx_process_pair_device(self._handle(), left.data_ptr(), right.data_ptr(), H, W,
                                                 left.stride(0), ctypes.byref(pp), _ptr(out_disp),
@@ -383,15 +392,17 @@ def _keep_until_done(t, stream):
 def postprocess_full_device(disp, crop, max_speckle_size=50, max_diff=1.0, apply_outlier_removal=True,
                             outlier_threshold=3.0, outlier_kernel=5, focal_length=None, baseline=None, doffs=0.0,
                             eps=1e-6, max_depth=None, stream=None, apply_hole_filling=False, fill_kernel=3,
-                            workspace=None):
+                            workspace=None, fill_method="inpaint"):
     """postprocess_disparity (postprocess.py:120-171) + depth on the device
-    (dsx_postprocess_full_ex_device): speckles -> outliers -> hole filling
-    (Telea 'inpaint' with radius ``fill_kernel`` when ``apply_hole_filling``) -> 3x3 median -> depth,
-    all enqueued on ``stream`` without host synchronisation.  ``disp``: float32 H x W HIP tensor.
+    (dsx_postprocess_device): speckles -> outliers -> hole filling when
+    ``apply_hole_filling`` (``fill_method`` 'inpaint': Telea with radius ``fill_kernel``; 'nearest':
+    ``fill_kernel`` masked dilations, stateless) -> 3x3 median -> depth, all enqueued on ``stream``
+    without host synchronisation.  ``disp``: float32 H x W HIP tensor.
     Returns (disp_cropped, depth or None) as HIP tensors.  ``workspace``: a ``FillWorkspace`` (default:
     one per device and stream), whose flag ``fill_holes_status(workspace)`` reports a timed-out fill."""
     import torch
 
+    method = _fill_method(fill_method)
     if disp.dtype != torch.float32 or disp.dim() != 2 or disp.stride(1) != 1 or not disp.is_cuda:
         raise ValueError("disp must be a float32 H x W device tensor with unit column stride")
     H, W = disp.shape
@@ -406,14 +417,26 @@ def postprocess_full_device(disp, crop, max_speckle_size=50, max_diff=1.0, apply
     wsobj = workspace if workspace is not None else default_workspace(disp.device, stream, "post")
     ws = wsobj.get(nbytes, disp.device, stream)
     sptr = _stream_ptr(stream)
-    rc = L.dsx_postprocess_full_ex_device(
-        disp.data_ptr(), H, W, disp.stride(0), int(crop), int(max_speckle_size), float(max_diff),
-        int(bool(apply_outlier_removal)), float(outlier_threshold), int(outlier_kernel),
-        int(fill_kernel) if apply_hole_filling else 0, out_disp.data_ptr(),
-        out_depth.data_ptr() if want_depth else None, float(focal_length or 0.0), float(baseline or 0.0),
-        float(doffs or 0.0), float(eps), float(max_depth or 0.0), int(max_depth is not None), ws.data_ptr(),
-        nbytes, sptr)
-    _dsx.check(rc, "dsx_postprocess_full_ex_device")
+    pp = _dsx.DsxPostParams()
+    pp.mode = _dsx.POST_MODE["full"]
+    pp.max_speckle_size = int(max_speckle_size)
+    pp.max_diff = float(max_diff)
+    pp.apply_outlier_removal = int(bool(apply_outlier_removal))
+    pp.outlier_threshold = float(outlier_threshold)
+    pp.outlier_kernel = int(outlier_kernel)
+    pp.fill_radius = int(fill_kernel) if apply_hole_filling else 0
+    pp.fill_method = method
+    pp.has_depth = int(want_depth)
+    pp.focal_length = float(focal_length or 0.0)
+    pp.baseline = float(baseline or 0.0)
+    pp.doffs = float(doffs or 0.0)
+    pp.eps = float(eps)
+    pp.max_depth = float(max_depth or 0.0)
+    pp.has_max_depth = int(max_depth is not None)
+    rc = L.dsx_postprocess_device(disp.data_ptr(), H, W, disp.stride(0), int(crop), ctypes.byref(pp),
+                                  out_disp.data_ptr(), out_depth.data_ptr() if want_depth else None, ws.data_ptr(),
+                                  nbytes, sptr)
+    _dsx.check(rc, "dsx_postprocess_device")
     _keep_until_done(ws, stream)
     return out_disp, out_depth
 
@@ -499,16 +522,21 @@ def default_workspace(device, stream, kind="fill"):
     return ws
 
 
-def fill_holes_device(disp, radius=5, out=None, stream=None, workspace=None, spin_limit=0, steps=0):
-    """fill_holes(disparity, method='inpaint', kernel_size=radius) on the device
-    (postprocess.py:72-118; dsx_fill_holes_ex_device): Telea inpainting of the pixels <= 0 in
-    cv2.inpaint's arrival-time order, equal to the host restatement (postprocess._telea_inpaint).
+def fill_holes_device(disp, radius=5, out=None, stream=None, workspace=None, spin_limit=0, steps=0,
+                      method="inpaint", path=0):
+    """fill_holes(disparity, method=method, kernel_size=radius) on the device (postprocess.py:72-118).
+    'inpaint' (dsx_fill_holes_ex_device): Telea inpainting of the pixels <= 0 in cv2.inpaint's
+    arrival-time order, equal to the host restatement (postprocess._telea_inpaint).  'nearest'
+    (dsx_fill_nearest_device): ``radius`` is the kernel_size k - k masked dilations with the ellipse
+    of radius k // 2, equal to the host ``fill_holes(method='nearest')``; stateless (no workspace
+    object, no status flag); ``path`` 0 auto, 1 fused (k <= 5), 2 stepwise; ``out`` must not be ``disp``.
     ``disp``: float32 H x W HIP tensor (unit column stride).  Asynchronous on ``stream``; returns the
     filled float32 H x W tensor.  ``workspace``: a ``FillWorkspace`` (default: one per device and
     stream).  ``spin_limit`` / ``steps``: dsx_fill_opts (tests: force a timeout / the persistent
     launch)."""
     import torch
 
+    method = _fill_method(method)
     if disp.dtype != torch.float32 or disp.dim() != 2 or disp.stride(1) != 1 or not disp.is_cuda:
         raise ValueError("disp must be a float32 H x W device tensor with unit column stride")
     H, W = disp.shape
@@ -519,6 +547,18 @@ def fill_holes_device(disp, radius=5, out=None, stream=None, workspace=None, spi
     if H == 0 or W == 0:
         return out
     L = _dsx.lib()
+    if method == _dsx.FILL_METHOD["nearest"]:
+        k, path = int(radius), int(path)
+        stepwise = path == _dsx.NEAREST_PATH["stepwise"] or (path == _dsx.NEAREST_PATH["auto"]
+                                                             and k > _dsx.NEAREST_FUSED_MAX)
+        nbytes = L.dsx_fill_nearest_workspace_bytes(H, W) if stepwise and k >= 2 else 0
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=disp.device) if nbytes else None
+        rc = L.dsx_fill_nearest_device(disp.data_ptr(), H, W, disp.stride(0), k, out.data_ptr(),
+                                       None if ws is None else ws.data_ptr(), nbytes, path, _stream_ptr(stream))
+        _dsx.check(rc, "dsx_fill_nearest_device")
+        if ws is not None:
+            _keep_until_done(ws, stream)
+        return out
     nbytes = L.dsx_fill_holes_workspace_bytes(H, W)
     wsobj = workspace if workspace is not None else default_workspace(disp.device, stream, "fill")
     ws = wsobj.get(nbytes, disp.device, stream)

@@ -449,6 +449,24 @@ def _telea_inpaint(img: np.ndarray, hole: np.ndarray, radius: int) -> np.ndarray
     return out.reshape(EH, EW)[1:-1, 1:-1].copy()
 
 
+def nearest_footprint(kernel_size) -> np.ndarray:
+    """The structuring element of fill_holes(method='nearest') (postprocess.py:108-110,
+    cv2.getStructuringElement(MORPH_ELLIPSE, (k, k)) as restated here): a (2 r + 1)^2 bool array,
+    r = k // 2, true where (dy / r)^2 + (dx / r)^2 <= 1.0 in float64; the single pixel for r = 0.
+    The one Python home of the rule (its C twin: dsx_fill_nearest_footprint)."""
+    r = int(kernel_size) // 2
+    if not r:
+        return np.ones((1, 1), bool)
+    yy, xx = np.mgrid[-r:r + 1, -r:r + 1]
+    return (yy / max(r, 1e-9)) ** 2 + (xx / max(r, 1e-9)) ** 2 <= 1.0
+
+
+def nearest_halfwidths(kernel_size) -> np.ndarray:
+    """``nearest_footprint`` as per-row half-widths, hw[dy + r] (-1: an empty row): the form the
+    device kernels take (every row of the footprint is a centred run)."""
+    return (nearest_footprint(kernel_size).sum(axis=1).astype(np.int32) - 1) // 2  # 2 w + 1 cells -> w; none -> -1
+
+
 def fill_holes(disparity, mask=None, method="inpaint", kernel_size=5):
     """postprocess.py:72-118."""
     filled = np.asarray(disparity, np.float32).copy()
@@ -457,9 +475,7 @@ def fill_holes(disparity, mask=None, method="inpaint", kernel_size=5):
     if method == "inpaint":
         return _telea_inpaint(filled, mask.astype(bool), int(kernel_size))
     if method == "nearest":
-        r = kernel_size // 2
-        yy, xx = np.mgrid[-r:r + 1, -r:r + 1]
-        ell = (yy / max(r, 1e-9)) ** 2 + (xx / max(r, 1e-9)) ** 2 <= 1.0 if r else np.ones((1, 1), bool)
+        ell = nearest_footprint(kernel_size)
         for _ in range(kernel_size):
             dil = ndimage.grey_dilation(filled, footprint=ell, mode="nearest")
             filled = np.where(mask, dil, filled)

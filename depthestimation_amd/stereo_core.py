@@ -25,6 +25,10 @@ Keys added to ``sgbm_params`` (accepted by ``configure_sgbm`` like the reference
                                        'sgm' adds semi-global aggregation over the SAD costs with
                                        the path set of 'sgbm_mode' and P1 = 8 bs^2, P2 = 32 bs^2 as
                                        _build_sgbm derives them, stereo_core.py:51-61)
+  'fill_method': 'inpaint' | 'nearest' (with 'hole_filling': fill_holes' method, postprocess.py:72-118.
+                                       'inpaint', the default and the reference's choice, is Telea's
+                                       march; 'nearest' is the iterated dilation - bounded, stateless,
+                                       nothing to time out, and fast enough for video)
 Keys of the reference that have no block-matching meaning are kept, validated and reported
 but do not change the result: 'prefilter_cap' unless 'cost' is 'bt', 'speckle_window_size' /
 'speckle_range' unless 'sgbm_post' is set, and 'sgbm_mode' / P1 / P2 while 'aggregation' is 'none'
@@ -120,6 +124,7 @@ class StereoCore:
             'aggregation': 'none',
             'sgbm_post': False,
             'lr_form': 'bm',
+            'fill_method': 'inpaint',
         }
         self._build_sgbm()
         self.disparity_map = None
@@ -132,6 +137,8 @@ class StereoCore:
         p = self.sgbm_params
         if p.get('aggregation', 'none') not in ('none', 'sgm'):
             raise ValueError("Invalid parameter value for 'aggregation': expected 'none' or 'sgm'")
+        if p.get('fill_method', 'inpaint') not in ('inpaint', 'nearest'):
+            raise ValueError("Invalid parameter value for 'fill_method': expected 'inpaint' or 'nearest'")
         self.P1 = 8 * p['block_size'] ** 2
         self.P2 = 32 * p['block_size'] ** 2
         self.mode = p.get('sgbm_mode', 'sgbm_3way') if p.get('sgbm_mode') in _SGBM_MODES else 'sgbm_3way'
@@ -206,7 +213,7 @@ class StereoCore:
                 max_speckle_size=int(100 * self.downscale_factor),
                 max_diff=1.0,
                 outlier_threshold=2.5,
-                fill_method='inpaint',
+                fill_method=self.sgbm_params.get('fill_method', 'inpaint'),
                 apply_outlier_removal=True,
                 apply_hole_filling=self.sgbm_params.get('hole_filling', False),
             )
@@ -275,37 +282,40 @@ class StereoCore:
     def process_pair_device(self, left, right, stream=None):
         """Device-resident ``_process_pair`` (stereo_core.py:162-200) for rectified uint8 HIP
         tensors: matcher -> crop -> post-processing -> depth, all in HBM.  Fast mode: 3x3 median
-        (SURVEY.md 8f row F1); otherwise speckle filter + outlier removal (+ Telea hole filling
-        with ``hole_filling``) + median (row F2).  Returns float32 HIP tensors
+        (SURVEY.md 8f row F1); otherwise speckle filter + outlier removal (+ hole filling
+        with ``hole_filling``, by ``fill_method``) + median (row F2).  Returns float32 HIP tensors
         (disparity_px, depth_m or None)."""
         p = self.sgbm_params
         f, B = p.get('focal_length'), p.get('baseline')
         doffs, eps, max_depth = p.get('doffs', 0.0), p.get('min_disp', 5.0), p.get('max_depth')
         fill = bool(p.get('hole_filling', False)) and not self.fast_mode
+        method = p.get('fill_method', 'inpaint')
+        timed = fill and method == 'inpaint'  # only Telea's persistent launch can time out
         if 'compute_disparity_device' not in self.__dict__ and self.sgbm is not None and \
                 getattr(self.sgbm, 'process_pair_device', None) is not None and \
                 getattr(self.sgbm, 'params', {}).get('float_mode', 'fixed') == 'fixed':
             # one C-ABI call per frame (dsx_process_pair_device): the handle owns the float map and
             # the post-processing workspace, and the hole filling's timeout flag
-            self._fill_check = self.sgbm.fill_status if fill else None
+            self._fill_check = self.sgbm.fill_status if timed else None
             return self.sgbm.process_pair_device(
                 left, right, fast_mode=self.fast_mode, max_speckle_size=int(100 * self.downscale_factor),
                 max_diff=1.0, apply_outlier_removal=True, outlier_threshold=2.5, outlier_kernel=5,
                 fill_radius=3 if p.get('hole_filling', False) else 0, focal_length=f, baseline=B, doffs=doffs,
-                eps=eps, max_depth=max_depth, stream=stream)
+                eps=eps, max_depth=max_depth, stream=stream, fill_method=method)
         disp = self.compute_disparity_device(left, right, stream=stream)
         self._fill_check = None
         if self.fast_mode:
             return postprocess_fast_device(disp, p['num_disp'], f, B, doffs, eps, max_depth, stream=stream)
         # fill_kernel 3: postprocess_disparity's default as _process_pair calls it (postprocess.py:165)
-        if fill:
+        if timed:
             ws = default_workspace(disp.device, stream, "post")
             self._fill_check = lambda: fill_holes_status(ws)
         return postprocess_full_device(disp, p['num_disp'], max_speckle_size=int(100 * self.downscale_factor),
                                        max_diff=1.0, apply_outlier_removal=True, outlier_threshold=2.5,
                                        outlier_kernel=5, focal_length=f, baseline=B, doffs=doffs, eps=eps,
                                        max_depth=max_depth, stream=stream,
-                                       apply_hole_filling=bool(p.get('hole_filling', False)), fill_kernel=3)
+                                       apply_hole_filling=bool(p.get('hole_filling', False)), fill_kernel=3,
+                                       fill_method=method)
 
     def disparity_to_depth(self, disp: np.ndarray, f_pixels: float, baseline_m: float, doffs: float = 0.0,
                            eps: float = 1e-6, max_depth: Optional[float] = None) -> np.ndarray:

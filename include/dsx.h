@@ -32,7 +32,9 @@
 extern "C" {
 #endif
 
-#define DSX_VERSION 106 /* 1.0.6: hole filling in OpenCV's own arithmetic and exact queue order, dsx_fill_holes_release,
+#define DSX_VERSION 106 /* additive since 1.0.6 (layouts unchanged): dsx_fill_nearest_*, dsx_postprocess_device,
+                           dsx_post_params.fill_method (a former reserved slot; 0 = as before);
+                           1.0.6: hole filling in OpenCV's own arithmetic and exact queue order, dsx_fill_holes_release,
                            dsx_shutdown;
                            1.0.5: arrival-order hole filling, per-workspace / per-handle fill status, dsx_fill_opts;
                            1.0.4: dsx_params.in_flight; 1.0.3: dsx_process_pair_device, dsx_fill_holes_status */
@@ -222,6 +224,33 @@ size_t dsx_fill_holes_workspace_bytes(int32_t H, int32_t W);
 int dsx_fill_holes_device(const void *d_disp, int32_t H, int32_t W, int64_t in_pitch, int32_t radius, void *d_out,
                           void *d_workspace, size_t workspace_bytes, void *hip_stream);
 
+/* fill_holes(disparity, method='nearest', kernel_size=k) on the device (postprocess.py:106-116): with
+ * mask = d <= 0 taken from the input and r = k / 2, k times f <- where(mask, dilate(f, ellipse(r)), f);
+ * every iteration reads only the previous one.  Taps outside the image are skipped (equal to the
+ * host's replicated border for these footprints); values <= 0 take part in the max; holes further
+ * than k * r from a valid pixel stay <= 0; k = 0 and k = 1 copy.  A float max only: bit-exact with the
+ * host restatement (depthestimation_amd/postprocess.py fill_holes).  Stateless: no grid barrier, no
+ * status flag, nothing to time out; calls on different streams are independent.
+ *
+ * dsx_fill_nearest_footprint (host only): the ellipse as per-row half-widths, halfwidths[dy + r] for
+ *   dy in [-r, r] (-1: an empty row), by numpy's float64 rule (dy / r)^2 + (dx / r)^2 <= 1.0 (r = 0:
+ *   the single pixel).  Writes 2 (k / 2) + 1 values and returns that count; DSX_EINVAL for
+ *   kernel_size outside [0, 31], a NULL array or cap too small.
+ * dsx_fill_nearest_device: d_disp float32 H x W, row pitch `in_pitch` elements; d_out contiguous
+ *   float32 H x W, not d_disp.  path: DSX_NEAREST_AUTO, DSX_NEAREST_FUSED (all iterations of a tile
+ *   in LDS, kernel_size <= DSX_NEAREST_FUSED_MAX, no workspace: d_workspace may be NULL) or
+ *   DSX_NEAREST_STEPWISE (one launch per iteration, any kernel_size <= 31; for kernel_size >= 2 it
+ *   needs >= dsx_fill_nearest_workspace_bytes(H, W) of workspace).  Auto is fused up to
+ *   DSX_NEAREST_FUSED_MAX, stepwise beyond.  Asynchronous on hip_stream. */
+#define DSX_NEAREST_AUTO 0
+#define DSX_NEAREST_FUSED 1
+#define DSX_NEAREST_STEPWISE 2
+#define DSX_NEAREST_FUSED_MAX 5
+int dsx_fill_nearest_footprint(int32_t kernel_size, int32_t *halfwidths, int32_t cap);
+size_t dsx_fill_nearest_workspace_bytes(int32_t H, int32_t W);
+int dsx_fill_nearest_device(const void *d_disp, int32_t H, int32_t W, int64_t in_pitch, int32_t kernel_size,
+                            void *d_out, void *d_workspace, size_t workspace_bytes, int32_t path, void *hip_stream);
+
 /* Launch shape of the march (tests and experiments; zero-initialised = the defaults). */
 typedef struct dsx_fill_opts {
     uint32_t spin_limit; /* grid-barrier spin bound of the persistent launch (0: default, ~2 s)    */
@@ -264,6 +293,8 @@ int dsx_shutdown(void);
  * times go to dsx_kernel_times when params.timing is set. */
 #define DSX_POST_FAST 1 /* fast_mode=True:  crop + medianBlur(3)                        */
 #define DSX_POST_FULL 2 /* fast_mode=False: crop + postprocess_disparity (the default)   */
+#define DSX_FILL_INPAINT 0 /* fill_method 'inpaint': Telea's march (dsx_fill_holes_device)        */
+#define DSX_FILL_NEAREST 1 /* fill_method 'nearest': iterated dilation (dsx_fill_nearest_device)  */
 typedef struct dsx_post_params {
     double max_diff;           /* 1.0   (stereo_core.py:179)                                        */
     double outlier_threshold;  /* 2.5   (stereo_core.py:180)                                        */
@@ -281,7 +312,9 @@ typedef struct dsx_post_params {
     int32_t has_max_depth;
     uint32_t fill_spin_limit;  /* hole filling's persistent-launch spin bound (0: default; tests)    */
     int32_t fill_steps;        /* hole filling's step launches: 0 adaptive, > 0 that many, < 0 none */
-    int32_t reserved[3];
+    int32_t fill_method;       /* DSX_FILL_INPAINT (0, Telea) | DSX_FILL_NEAREST: fill_radius is then the */
+                               /* kernel_size of fill_holes(method='nearest'), 0..31                     */
+    int32_t reserved[2];
 } dsx_post_params;
 
 /* dL, dR: device uint8 H x W (row stride `stride_bytes`), rectified.  d_out_disp / d_out_depth:
@@ -290,6 +323,15 @@ typedef struct dsx_post_params {
 int dsx_process_pair_device(dsx_handle *h, const void *dL, const void *dR, int32_t H, int32_t W,
                             int64_t stride_bytes, const dsx_post_params *pp, void *d_out_disp,
                             void *d_out_depth, void *hip_stream);
+
+/* The stand-alone post-processing chain with its parameters in a dsx_post_params (mode DSX_POST_FULL):
+ * what dsx_postprocess_full_ex_device runs, plus fill_method (and fill_spin_limit / fill_steps for the
+ * Telea march).  d_out_depth is written only when has_depth.  d_workspace: >=
+ * dsx_postprocess_workspace_bytes(H, W, crop); it carries the Telea timeout flag, which 'nearest'
+ * neither raises nor consults.  Asynchronous on hip_stream. */
+int dsx_postprocess_device(const void *d_disp, int32_t H, int32_t W, int64_t in_pitch, int32_t crop,
+                           const dsx_post_params *pp, void *d_out_disp, void *d_out_depth, void *d_workspace,
+                           size_t workspace_bytes, void *hip_stream);
 
 /* Per-frame rectification on the device, replacing cv2.cvtColor(BGR2GRAY)
  * + cv2.remap(INTER_LINEAR) of rectify.py:183-186 (cached-maps path) and stereo_core.py:155-159:

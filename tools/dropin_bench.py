@@ -6,7 +6,7 @@ depthlib/stereo_core.py:162-200, postprocess.py:120-171), frames resident in HBM
 Reports per config: host wall ms per frame (back to back, one sync at the end), GPU ms per frame
 (stream events around the loop) and the handle's per-kernel HIP-event breakdown.
 
-usage: python tools/dropin_bench.py [--configs c2r c4] [--frames 200]
+usage: python tools/dropin_bench.py [--configs c2r c4] [--frames 200] [--hole-filling inpaint|nearest]
 """
 import argparse
 import json
@@ -30,6 +30,8 @@ def main():
     ap.add_argument("--frames", type=int, default=200)
     ap.add_argument("--legacy-post", action="store_true",
                     help="the round-3 four-launch speckle union-find (DSX_POST_LEGACY) for a before/after")
+    ap.add_argument("--hole-filling", choices=["inpaint", "nearest"], default=None,
+                    help="run with hole_filling=True and this fill_method (default: hole filling off)")
     args = ap.parse_args()
     if args.legacy_post:
         os.environ["DSX_POST_LEGACY"] = "1"
@@ -43,6 +45,8 @@ def main():
             frames.append((torch.from_numpy(L).to(dev), torch.from_numpy(R).to(dev)))
         core = StereoCore()
         core.configure_sgbm(num_disp=D, block_size=cfg["block_size"], focal_length=700.0, baseline=0.1)
+        if args.hole_filling:
+            core.configure_sgbm(hole_filling=True, fill_method=args.hole_filling)
         stream = torch.cuda.current_stream(dev)
         for i in range(20):
             core.estimate_depth_device(*frames[i % 4])
@@ -60,7 +64,8 @@ def main():
                 "uniqueness_ratio": core.sgbm_params["uniqueness_ratio"],
                 "disp12_max_diff": core.sgbm_params["disp12_max_diff"], "fast_mode": core.fast_mode,
                 "wall_ms_per_frame": round(wall, 4), "gpu_ms_per_frame": round(gpu, 4),
-                "mpix_s_wall": round(H * W / wall / 1e3, 1), "legacy_post": bool(args.legacy_post)}
+                "mpix_s_wall": round(H * W / wall / 1e3, 1), "legacy_post": bool(args.legacy_post),
+                "hole_filling": args.hole_filling}
         # per-kernel breakdown: the same pipeline through a matcher with HIP-event timing
         core.sgbm = HipBlockMatcher(**dict(core.sgbm.params, timing=True))
         for i in range(10):

@@ -1,4 +1,4 @@
-"""Device post-processing timings (+ hole filling) at a config's size, next to
+"""Device post-processing timings (+ hole filling by both methods) at a config's size, next to
 the matcher: stream events around each device call, median of N runs, on the matcher's own output
 for a synthetic frame.  One JSON line per config.
 
@@ -62,6 +62,12 @@ def main():
                 holes = int((d2 <= 0).sum().item())
                 t_fill = timed(lambda: fill_holes_device(d2, radius=3, stream=stream), args.runs, stream)
                 line.update({"fill_holes_ms": round(t_fill, 4), "hole_pixels": holes})
+                # fill_holes(method='nearest') on the same map: kernel_size 3 and 5, both device paths
+                out = torch.empty_like(d2)
+                line["fill_nearest_ms"] = {
+                    f"k{k}_{name}": round(timed(lambda: fill_holes_device(d2, radius=k, method="nearest", path=path,
+                                                                          out=out, stream=stream), args.runs, stream), 4)
+                    for k in (3, 5) for name, path in (("fused", 1), ("stepwise", 2))}
             except ImportError:
                 pass
         bm.close()
