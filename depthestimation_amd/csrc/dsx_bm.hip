@@ -42,6 +42,22 @@
 constexpr int kWpe = 3;     // waves per SIMD the fused pass is compiled for (SAD, and SSD below 4 waves)
 constexpr int kWpeSsd = 4;  // SSD blocks of >= 4 waves
 
+// Row-step forms that can be switched off for an A/B build (tools/variant_bm.sh -DDSX_ROWSTEP_ATID=0
+// / -DDSX_ROWSTEP_KEY2=0 / -DDSX_ROWSTEP_MERGE=0): the lane-indexed tile stores, the key-tree argmin and the
+// merged row staging of the pair layout.
+#ifndef DSX_ROWSTEP_ATID
+#define DSX_ROWSTEP_ATID 1
+#endif
+#ifndef DSX_ROWSTEP_KEY2
+#define DSX_ROWSTEP_KEY2 1
+#endif
+#ifndef DSX_ROWSTEP_MERGE
+#define DSX_ROWSTEP_MERGE 1
+#endif
+constexpr bool kRowstepMerge = DSX_ROWSTEP_MERGE;  // one load and one 16-B store per staged row
+constexpr bool kRowstepAtid = DSX_ROWSTEP_ATID;
+constexpr bool kRowstepKey2 = DSX_ROWSTEP_KEY2;
+
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -92,6 +108,38 @@ __device__ __forceinline__ uint32_t sad_hi_u8(uint32_t a, uint32_t b, uint32_t c
 __device__ __forceinline__ uint32_t min_shr1(uint32_t src, uint32_t key) {
     asm("s_nop 1\n\tv_min_u32_dpp %0, %1, %0 wave_shr:1 row_mask:0xf bank_mask:0xf" : "+v"(key) : "v"(src));
     return key;
+}
+// Eight lane-indexed LDS stores: lane l writes v[j] to M0[15:0] + OFF0 + j * STRIDE + 4 l (bytes, LDS
+// address space), j = 0..7.  ds_write_addtid_b32 takes no address VGPR, so a store moves one source
+// dword to the LDS instead of two, and the per-row base additions of the ds_write2_b32 form go.
+// M0 is set inside the statement (one SALU op per eight stores), so nothing depends on the compiler
+// leaving M0 alone between statements; s_nop 0: one wait state between an SALU write of M0 and an
+// add-TID LDS instruction.  hipcc does not count LDS operations inside inline asm: in order within a
+// wave, but a multi-wave block must drain lgkmcnt itself before its barrier (lds_drain below).
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+template <int OFF0, int STRIDE>
+__device__ __forceinline__ void lds_store8_addtid(uint32_t m0base, const uint32_t (&v)[8]) {
+    static_assert(OFF0 >= 0 && OFF0 + 7 * STRIDE < 65536, "16-bit offset field");
+    asm volatile("s_mov_b32 m0, %8\n\ts_nop 0\n\t"
+                 "ds_write_addtid_b32 %0 offset:%9\n\t"
+                 "ds_write_addtid_b32 %1 offset:%10\n\t"
+                 "ds_write_addtid_b32 %2 offset:%11\n\t"
+                 "ds_write_addtid_b32 %3 offset:%12\n\t"
+                 "ds_write_addtid_b32 %4 offset:%13\n\t"
+                 "ds_write_addtid_b32 %5 offset:%14\n\t"
+                 "ds_write_addtid_b32 %6 offset:%15\n\t"
+                 "ds_write_addtid_b32 %7 offset:%16"
+                 :
+                 : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]), "s"(m0base),
+                   "n"(OFF0), "n"(OFF0 + STRIDE), "n"(OFF0 + 2 * STRIDE), "n"(OFF0 + 3 * STRIDE), "n"(OFF0 + 4 * STRIDE),
+                   "n"(OFF0 + 5 * STRIDE), "n"(OFF0 + 6 * STRIDE), "n"(OFF0 + 7 * STRIDE)
+                 : "memory", "m0");
+}
+#pragma clang diagnostic pop
+__device__ __forceinline__ void lds_drain() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+__device__ __forceinline__ uint32_t lds_offset(const uint8_t *p) {
+    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint8_t *)p;
 }
 __host__ __device__ constexpr int rnd16(int v) { return (v + 15) & ~15; }
 template <int R, bool SSD, int NW>
@@ -255,6 +303,42 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
     // -8 %, C4 +4 % in flight, C2r +1 %); the one-disparity layouts measured slower with it (C3
     // 322.7 -> 330 us, C1 13.19 -> 13.24 us) and keep the first form.
     constexpr bool RL2 = !SSD;
+    // RL2, FAST: the lane's byte offsets into the reference / searched row.  The row loop passes them
+    // through an empty asm once per step (in place, no instruction): left loop-invariant, their zero
+    // extensions are hoisted as 64-bit pairs and every load then pays a v_lshl_add_u64 for the 64-bit
+    // address form instead of taking SGPR base + 32-bit VGPR offset.
+    uint32_t ofs_r = (uint32_t)(x0 - R + 4 * min(tid, NC4 - 1));
+    uint32_t ofs_s = side == 1 ? (uint32_t)(PB + 4 * min(tid, NJ4 - 1)) : (uint32_t)(PB - 4 * min(tid, NJ4 - 1) - 3);
+    // MRG (pair layout, FAST copy, outside the LR pass): a staged row takes one load and one 16-B store.
+    // Lanes tid < NJ4 own a searched dword as before, lanes NJ4 <= tid < NJ4 + NC4 a reference dword
+    // (the rest repeat the last one and store nothing).  The two images have different bases, so a
+    // lane holds a 64-bit base per segment and a row costs one 64-bit add (the wave-uniform row
+    // offset) and one load.  Per-lane v_perm_b32 selectors bring both byte orders - searched entries
+    // run down with the byte index in the left forms, reference columns up - to one zero-extending
+    // unpack of four ops, and one ds_write_b128 with a per-lane address stores the row.  Per step:
+    // 2 loads, 2 stores and 10 VALU fewer.  The builds at their register budget keep the two-load form: the
+    // LR pass, and the volume pass and the 15x15 OpenCV-keys pass, which spill with the merged one (32 B
+    // at R = 4, 8 B).
+    constexpr bool MRG = kRowstepMerge && RL2 && FAST && SIDE != 3 && SIDE != 2 && !(SIDE == 4 && R >= 7);
+    static_assert(!MRG || NJ4 + NC4 <= NT, "merged staging: a lane per staged dword");
+    const bool m_s = tid < NJ4;
+    const int m_r = min(tid - NJ4, NC4 - 1);  // reference dword of a non-search lane
+    const uint8_t *m_base = m_s ? a.src + fin + ofs_s : a.ref + fin + (uint32_t)(x0 - R + 4 * m_r);
+    const bool m_dn = m_s && side != 1;  // bytes 3, 2, 1, 0 -> words 0 .. 3
+    const uint32_t m_sel0 = m_dn ? 0x0C0C0C03u : 0x0C0C0C00u, m_sel1 = m_dn ? 0x0C0C0C02u : 0x0C0C0C01u,
+                   m_sel2 = m_dn ? 0x0C0C0C01u : 0x0C0C0C02u, m_sel3 = m_dn ? 0x0C0C0C00u : 0x0C0C0C03u;
+    const uint32_t m_lane = m_s ? (uint32_t)(16 * tid) : (uint32_t)(G::SROW + 16 * m_r);  // byte offset in a slot
+    auto ldm = [&](int r, uint32_t &w) __attribute__((always_inline)) {
+        const int yy = clampi2(r, 0, H - 1);
+        long ro = (long)yy * stride;
+        asm("" : "+s"(ro));  // pinned to SGPRs: left free, the product is folded into one v_mad_u64_u32 per load
+        w = *reinterpret_cast<const uint32_t *>(m_base + ro);
+    };
+    auto stm = [&](uint8_t *sp, uint32_t w) __attribute__((always_inline)) {
+        if (tid < NJ4 + NC4)
+            *reinterpret_cast<uint4 *>(sp) = make_uint4(__builtin_amdgcn_perm(0u, w, m_sel0), __builtin_amdgcn_perm(0u, w, m_sel1),
+                                                        __builtin_amdgcn_perm(0u, w, m_sel2), __builtin_amdgcn_perm(0u, w, m_sel3));
+    };
     auto ld = [&](int r, uint32_t &w0, uint32_t &w1, uint32_t &w2, uint32_t &w3, uint32_t &rf) __attribute__((always_inline)) {
         const int yy = clampi2(r, 0, H - 1);
         // The row base is wave-uniform and the lane's part a small non-negative offset (FAST:
@@ -276,8 +360,11 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
         row8 *srow = (row8 *)srow_, *rrow = (row8 *)rrow_;
         const int tr = min(tid, NC4 - 1);
         if constexpr (FAST) {
-            if constexpr (RL2) rf = *reinterpret_cast<row32 *>(rrow + (uint32_t)(x0 - R + 4 * tr));
-            else rf = *reinterpret_cast<row32 *>(rrow + x0 - R + 4 * tr);
+            if constexpr (RL2) {
+                rf = *reinterpret_cast<row32 *>(rrow + ofs_r);
+            } else {
+                rf = *reinterpret_cast<row32 *>(rrow + x0 - R + 4 * tr);
+            }
         } else {
             uint32_t v = 0;
 #pragma unroll
@@ -288,7 +375,7 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
             const int tj = min(tid, NJ4 - 1);
             row8 *p;
             if constexpr (RL2) {
-                p = side == 1 ? srow + (uint32_t)(PB + 4 * tj) : srow + (uint32_t)(PB - 4 * tj - 3);
+                p = srow + ofs_s;
             } else {
                 // The one-wave LR builds (at their register budget) add one int offset: (srow + PB) - 4 * tj
                 // keeps a 64-bit -4 * tj live across the segments, which spilled there.
@@ -340,6 +427,22 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
             }
         }
         if (tid < NJ4) *reinterpret_cast<uint4 *>(smem + sl * SLOT + 16 * tid) = make_uint4(w0, w1, w2, w3);
+    };
+    // st() of the pair layout's row loop (RL2, never f32), at sp = the lane's 16 bytes of the slot's
+    // searched row (smem + sl * SLOT + 16 * tid).  Apart from st(), which the one-disparity layouts and
+    // the init keep word for word: routed through one body, their instruction streams changed.
+    auto st_at = [&](uint8_t *sp, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t rf) __attribute__((always_inline)) {
+        if (tid < NC4)
+            *reinterpret_cast<uint4 *>(sp + G::SROW) = make_uint4(rf & 0xFFu, (rf >> 8) & 0xFFu, (rf >> 16) & 0xFFu, rf >> 24);
+        if constexpr (FAST) {
+            const uint32_t dw = w0;
+            if (side == 1) {
+                w0 = dw & 0xFFu; w1 = (dw >> 8) & 0xFFu; w2 = (dw >> 16) & 0xFFu; w3 = dw >> 24;
+            } else {
+                w0 = dw >> 24; w1 = (dw >> 16) & 0xFFu; w2 = (dw >> 8) & 0xFFu; w3 = dw & 0xFFu;
+            }
+        }
+        if (tid < NJ4) *reinterpret_cast<uint4 *>(sp) = make_uint4(w0, w1, w2, w3);
     };
     // reference pixels of slot sl, columns [c0, c0+CW): broadcast 16-B LDS reads
     auto ref_chunk = [&](int sl, int c0, uint32_t(&rw)[CW]) __attribute__((always_inline)) {
@@ -601,6 +704,8 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
     const bool dodd = !SSD && (D & 1);
     const bool lane_writes = d0 < D;
 
+    // RL2: the lane's bytes in slot par ^ 2 of the first step
+    uint32_t stg = (MRG ? m_lane : (uint32_t)(16 * tid)) + (uint32_t)((2 - (yb & 1) * 2) * SLOT);
     for (int y = yb; y < ye; ++y) {
         const Bm2Args &a = kargs_row<SIDE == 3>(a_in);
 #ifdef DSX_STAMPS
@@ -611,8 +716,14 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
             // issue priority by progress quartile: waves that are behind (the younger ones on a
             // SIMD, which lose age arbitration) take the VALU first, so co-resident waves finish
             // together instead of leaving the last one alone on its SIMD
+            // sign bits, not compares: the sum of three wave-uniform bools came out as v_cndmask +
+            // v_readfirstlane pairs; (pe - 1 - dn) >> 31 stays on the scalar unit (|values| < 2^30)
             const int dn = done0 + (y - yb);
-            const int q = (dn >= pe[0]) + (dn >= pe[1]) + (dn >= pe[2]);
+            // Pair layout only: with it C3 (bm2<5, SSD, 4, 3>) ran 321.4 -> 324.5 us, so the
+            // one-disparity layouts keep the compares and their instruction streams.
+            const int q = RL2 ? (int)(((uint32_t)(pe[0] - 1 - dn) >> 31) + ((uint32_t)(pe[1] - 1 - dn) >> 31) +
+                                      ((uint32_t)(pe[2] - 1 - dn) >> 31))
+                              : (dn >= pe[0]) + (dn >= pe[1]) + (dn >= pe[2]);
             if (q != qcur) {
                 qcur = q;
                 switch (q) {
@@ -623,6 +734,7 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
                 }
             }
         }
+        if constexpr (RL2 && FAST && !MRG) asm volatile("" : "+v"(ofs_r), "+v"(ofs_s));
         const int par = (y & 1) * 2;  // slots {par, par+1} = {new row y+R, old row y-R-1}
         const bool more = y + 1 < ye;
         // prefetch the next step's entering / leaving rows (+ its dR segment); lands during this step.
@@ -631,7 +743,10 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
         // are dead.  First form (!RL2): under `if (more)`; writing the zeros then waits for the
         // previous step's loads and stores (s_waitcnt vmcnt(0) at the loop header).
         uint32_t pn0 = 0, pn1 = 0, pn2 = 0, pn3 = 0, pnr = 0, po0 = 0, po1 = 0, po2 = 0, po3 = 0, por = 0;
-        if (RL2 || more) {
+        if constexpr (MRG) {
+            ldm(y + 1 + R, pn0);
+            ldm(y - R, po0);
+        } else if (RL2 || more) {
             ld(y + 1 + R, pn0, pn1, pn2, pn3, pnr);
             ld(y - R, po0, po1, po2, po3, por);
         }
@@ -698,6 +813,10 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
         // ---- horizontal running box sum -> LDS tile (pixel k, disparity d0..) ----
         {
             uint8_t *tb = tile + d0 * CB;
+            // Tile stores without an address VGPR (lds_store8_addtid): the pair layout outside the LR
+            // pass, whose stores sit between the diagonal keys of single pixels.  The one-disparity
+            // layouts keep ds_write_b32 (not measured with this form).
+            constexpr bool ATID = kRowstepAtid && !SSD && SIDE != 3;
             auto abits = [](acc_t v) __attribute__((always_inline)) -> uint32_t {
                 if constexpr (FSS) return __float_as_uint(v);
                 else if constexpr (SSD) return v;
@@ -820,6 +939,26 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
                 if constexpr (!SSD) {
                     if (Ao != 0xFFFFFFFFu && xa - 1 >= 0 && xa - 1 < W) atomicMin(krow + xa - 1, Ao);
                 }
+            } else if (ATID && lane_writes) {
+                // lane-indexed stores, eight pixels per statement: tb = tile + wv * LDW * CB + 4 * lane
+                static_assert(!ATID || (TX % 8 == 0 && G::LDW * CB == 256), "addtid: a lane's tile bytes are 4 * lane");
+                if constexpr (ATID) {
+                const uint32_t mb = lds_offset(tile) + (uint32_t)wvu * (uint32_t)(G::LDW * CB);
+                auto grp = [&](auto k0c) __attribute__((always_inline)) {
+                    constexpr int k0 = decltype(k0c)::value;
+                    uint32_t v[8];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        if (k0 + j > 0) acc = add_sub2(acc, cs[k0 + j + 2 * R], cs[k0 + j - 1]);
+                        v[j] = as1(acc);
+                    }
+                    lds_store8_addtid<k0 * PITCH, PITCH>(mb, v);
+                };
+                grp(std::integral_constant<int, 0>{});
+                grp(std::integral_constant<int, 8>{});
+                grp(std::integral_constant<int, 16>{});
+                grp(std::integral_constant<int, 24>{});
+                }
             } else if (lane_writes) {
 #pragma unroll
                 for (int k = 0; k < TX; ++k) {
@@ -849,6 +988,9 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
             }
         }
         DSX_STAMP(3);
+        // the lane-indexed tile stores are invisible to the compiler's lgkmcnt bookkeeping: drained
+        // by hand before the barrier that publishes the tile to the block's other waves
+        if constexpr (kRowstepAtid && !SSD && SIDE != 3 && NW > 1) lds_drain();
         block_sync<NW>();
         DSX_STAMP(4);
         // The prefetched rows go to LDS here, before the epilogue's output stores: the loads have
@@ -859,9 +1001,25 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
         // block has passed the mid-step barrier above since then, and the barrier that ends the
         // step orders these writes before step y + 1 reads them (the end barrier of step y - 1 alone
         // already separates them from their last readers).  The epilogue reads the tile only.
-        if (RL2 && more) {
-            st(par ^ 2, pn0, pn1, pn2, pn3, pnr);
-            st((par ^ 2) + 1, po0, po1, po2, po3, por);
+        if constexpr (RL2) {
+            // the lane's staging address alternates between slots 0 and 2: carried across the steps and
+            // flipped with one subtraction (rebuilt from par, it came out as one v_mad per store)
+            if constexpr (MRG) {
+                if (more) {
+                    stm(smem + stg, pn0);
+                    stm(smem + stg + SLOT, po0);
+                }
+                stg = (2 * m_lane + (uint32_t)(2 * SLOT)) - stg;
+            } else if constexpr (SIDE != 3) {
+                if (more) {
+                    st_at(smem + stg, pn0, pn1, pn2, pn3, pnr);
+                    st_at(smem + stg + SLOT, po0, po1, po2, po3, por);
+                }
+                stg = (uint32_t)(32 * tid + 2 * SLOT) - stg;
+            } else if (more) {  // LR pass, at its register budget: no carried address (R = 1 spilled 16 B more)
+                st(par ^ 2, pn0, pn1, pn2, pn3, pnr);
+                st((par ^ 2) + 1, po0, po1, po2, po3, por);
+            }
         }
         DSX_STAMP(5);
         if constexpr (side == 2) {
@@ -896,8 +1054,11 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
             }
             // Two argmin forms, chosen per instantiation from measurements (r01e): the key tree
             // wins on the LR pass (C3, C4) and 15x15 windows (C5); the compare/select scan keeps
-            // the SIDE 0 pass at <= 11x11 at 151 VGPRs (the key tree costs C2 +7 %).
+            // the SIDE 0 pass at <= 11x11 at 151 VGPRs (the key tree costs C2 +7 %).  That scan is
+            // what the one-disparity layouts still take there; the pair layout has its own, cheaper
+            // keys (KEY2 below: C2 54.5 -> 53.8 us against the scan).
             constexpr bool KEYS = SIDE == 3 || R >= 6;
+            constexpr bool KEY2 = kRowstepKey2 && !KEYS && !SSD;
             uint32_t cb, dl;
             if constexpr (KEYS) {
                 // lowest-d argmin without compare/select scans: keys (cost << GB | global block) give
@@ -932,6 +1093,31 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
                     }
                     dl = (uint32_t)(h * DSL + 8 * bsel + (int)(k8 & 7u));
                 }
+            } else if constexpr (KEY2) {
+                // Keys again, in the cheapest form for the packed u16 costs: the block key is one
+                // v_lshl_or_b32 with an inline block index (the lane's h * NB is or-ed in once, after the
+                // lane's own minimum: it is common to the lane's keys and its bits are clear in them), and
+                // an element key keeps the cost where it lies - low halves shifted up 16 (v_lshl_or_b32),
+                // high halves masked in place (v_and_or_b32) - with the element index in the low bits.
+                // Every lane keys the block of that index in its own slice (no branch); only the owner's
+                // result counts.  12 + 12 VALU against 20 + 22 with 15 s_nop for the scans below.
+                static_assert((NB & (NB - 1)) == 0, "block index bits");
+                constexpr int GB = Dp / 8 <= 16 ? 4 : (Dp / 8 <= 32 ? 5 : 6);
+                uint32_t kmin = 0xFFFFFFFFu;
+    #pragma unroll
+                for (int i = 0; i < NB; ++i) kmin = umin2(kmin, (bs[i] << GB) | (uint32_t)i);
+                kmin = gmin<TPP>(kmin | (uint32_t)(h * NB));
+                cb = kmin >> GB;
+                const uint32_t gblk = kmin & ((1u << GB) - 1u);
+                const uint4 v = *reinterpret_cast<const uint4 *>(px + 16 * (gblk & (NB - 1)));
+                const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
+                uint32_t k8 = 0xFFFFFFFFu;
+    #pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    k8 = umin2(k8, (w4[q] << 16) | (uint32_t)(2 * q));
+                    k8 = umin2(k8, (w4[q] & 0xFFFF0000u) | (uint32_t)(2 * q + 1));
+                }
+                dl = (int)(gblk / NB) == h ? gblk * 8 + (k8 & 7u) : 0xFFFFu;
             } else {
                 uint32_t lmin = bs[0];
     #pragma unroll

@@ -8,6 +8,10 @@ loop of an instantiation (the unaligned-dword copy and the clamped-byte copy of 
   * where each vmcnt wait sits in the step, counted from the step's first global load: how many
     of the loop's global loads and global_store_* / global_atomic_* precede it (a wait behind all
     of the stores is in the step's tail or at the next step's header);
+  * the ds_* instructions by opcode and the LDS-path cycles per wave they amount to (LDS_CYCLES below:
+    cycles per wave-instruction for conflict-free accesses; a store's cycles are those of moving its
+    address and data dwords to the LDS).  Static counts over every block of the loop, the branches a
+    benchmark step does not take included (odd-D overwrite, uniqueness re-reads, edge overwrites);
   * the kernel's VGPRs, scratch bytes and LDS bytes per block (Geo in dsx_bm.hip, restated here).
 
 It reports; it gates nothing.
@@ -27,6 +31,27 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from valu_roofline import BENCH_KERNELS, ROOT, blocks, function_body, kernel_label, row_loops, symbol  # noqa: E402
 
 ORDER = ["c2", "c2r", "c4", "c5", "c1", "c3"]
+
+
+# LDS cycles per wave64 instruction, conflict-free (measured on MI355X; stores: 2 cycles per source
+# dword moved to the LDS, the 12- and 16-byte forms more; ds_write_addtid_b32 has no address dword)
+LDS_CYCLES = {
+    "ds_read_u8": 2, "ds_read_i8": 2, "ds_read_u16": 2, "ds_read_i16": 2, "ds_read_u16_d16": 2, "ds_read_u16_d16_hi": 2,
+    "ds_read_b32": 2, "ds_read_b64": 2, "ds_read_b96": 8, "ds_read_b128": 4, "ds_read2_b32": 4, "ds_read2_b64": 8,
+    "ds_write_b8": 4, "ds_write_b16": 4, "ds_write_b32": 4, "ds_write_b64": 6, "ds_write2_b32": 6,
+    "ds_write_b96": 10, "ds_write_b128": 13, "ds_write2_b64": 13, "ds_write_addtid_b32": 2,
+}
+
+
+def lds_report(ops):
+    """(text, cycles) for the ds_* instructions of a loop; opcodes without a table entry are listed at 0."""
+    cnt = {}
+    for _, op, _ in ops:
+        if op.startswith("ds_"):
+            cnt[op] = cnt.get(op, 0) + 1
+    cyc = sum(n * LDS_CYCLES.get(op, 0) for op, n in cnt.items())
+    txt = ", ".join(f"{op} {n}" + ("" if op in LDS_CYCLES else " (no table entry)") for op, n in sorted(cnt.items()))
+    return txt, cyc
 
 
 def rnd16(v):
@@ -80,6 +105,10 @@ def report(asm, name, out):
         out(f"  loop {bl[i][0]} .. {bl[j][0]}: VALU {nvalu((i, j))}, ds_read2_b64 {cnt('ds_read2_b64')}, "
             f"ds_read_b64 {cnt('ds_read_b64')}, v_mad_u64_u32 {cnt('v_mad_u64_u32')}, "
             f"global loads {cnt('global_load')}, global stores/atomics {cnt('global_store') + cnt('global_atomic')}")
+        txt, cyc = lds_report(ops)
+        out(f"    LDS: {txt}")
+        out(f"    LDS-path cycles per wave (static): {cyc}; s_nop {cnt('s_nop')}, v_readfirstlane {cnt('v_readfirstlane')}, "
+            f"v_lshl_add_u64 {cnt('v_lshl_add_u64')}")
         # The compiler lays the blocks of a step out of program order (the column update and the
         # box phase sit behind the stores in the listing), so positions are taken from the control
         # flow: op k leads to op k + 1 (unless it is s_branch) and to its branch target.  The step
