@@ -16,16 +16,19 @@ from .stereo_core import StereoCore
 class StereoDepthEstimator:
     """Depth from a still stereo pair."""
 
-    def __init__(self, left_source=None, right_source=None, downscale_factor=1.0):
+    def __init__(self, left_source=None, right_source=None, downscale_factor=1.0, device_downscale=False):
         if downscale_factor <= 0 or downscale_factor > 1.0:
             raise ValueError("downscale_factor must be between 0 and 1.")
         self.downscale_factor = downscale_factor
+        # True: the pair is loaded at full size and downscaled on the GPU (StereoCore.estimate_depth's
+        # input_scale) instead of by load_stereo_pair (input.py:38-43) - the same maps
+        self.device_downscale = bool(device_downscale)
         self.core = StereoCore(downscale_factor=downscale_factor)
         self.left_source = None
         self.right_source = None
         if left_source is not None and right_source is not None:
-            self.left_source, self.right_source = load_stereo_pair(left_source, right_source,
-                                                                   downscale_factor=downscale_factor)
+            self.left_source, self.right_source = load_stereo_pair(
+                left_source, right_source, downscale_factor=1.0 if self.device_downscale else downscale_factor)
         self.sgbm = None
         self.disparity_map = None
         self.depth_map = None
@@ -41,7 +44,8 @@ class StereoDepthEstimator:
         """StereoDepthEstimator.py:90-107."""
         if self.left_source is None or self.right_source is None:
             raise ValueError("Left and right sources must be provided for depth estimation.")
-        disparity_px, depth_m = self.core.estimate_depth(self.left_source, self.right_source)
+        kw = {"input_scale": self.downscale_factor} if self.device_downscale else {}
+        disparity_px, depth_m = self.core.estimate_depth(self.left_source, self.right_source, **kw)
         self.disparity_map = disparity_px
         self.depth_map = depth_m
         return disparity_px, depth_m

@@ -30,7 +30,7 @@ from .threaded_stereo import ThreadedStereoCapture
 class StereoDepthEstimatorVideo:
     def __init__(self, left_source=None, right_source=None, downscale_factor=1.0, visualize_live=False,
                  saving_path=None, fast_mode=False, use_threading=True, target_fps=30, drop_frames=False,
-                 visualize_gray=False, rank=None, world_size=None, devices=None) -> None:
+                 visualize_gray=False, rank=None, world_size=None, devices=None, device_downscale=False) -> None:
         self.left_source = left_source
         self.right_source = right_source
         self.downscale_factor = downscale_factor
@@ -46,6 +46,9 @@ class StereoDepthEstimatorVideo:
         self.rank = env.rank if rank is None else int(rank)
         self.world_size = env.world_size if world_size is None else int(world_size)
         self.devices = None if devices is None else [int(d) for d in devices]
+        # True: frames stay full size through capture and upload, and the downscale (input.py:63-67,
+        # threaded_stereo.py:45-47) runs on the GPU (StereoCore.estimate_depth's input_scale) - same maps
+        self.device_downscale = bool(device_downscale)
         self.core = StereoCore(downscale_factor=downscale_factor, fast_mode=fast_mode)
         if self.world_size > 1:
             self.core.configure_sgbm(device=env.local_rank if rank is None else self.core.sgbm_params['device'])
@@ -57,8 +60,9 @@ class StereoDepthEstimatorVideo:
         """This rank's frame pairs: the others are skipped at the source without being decoded
         (every rank used to decode every frame and drop the ones it did not own)."""
         r, n = (0, 1) if self.devices else (self.rank, self.world_size)
+        factor = 1.0 if self.device_downscale else self.downscale_factor
         if self.use_threading:
-            cap = ThreadedStereoCapture(self.left_source, self.right_source, downscale_factor=self.downscale_factor,
+            cap = ThreadedStereoCapture(self.left_source, self.right_source, downscale_factor=factor,
                                         drop_frames=self.drop_frames, rank=r, world_size=n)
             cap.start()
             try:
@@ -70,7 +74,7 @@ class StereoDepthEstimatorVideo:
             finally:
                 cap.stop()
         else:
-            yield from stereo_stream(self.left_source, self.right_source, downscale_factor=self.downscale_factor,
+            yield from stereo_stream(self.left_source, self.right_source, downscale_factor=factor,
                                      rank=r, world_size=n)
 
     def estimate_depth(self):
@@ -84,8 +88,9 @@ class StereoDepthEstimatorVideo:
             yield from self._estimate_multi_device()
             return
         frame_start_time = time.time()
+        kw = {"input_scale": self.downscale_factor} if self.device_downscale else {}
         for left_frame, right_frame in self._frames():  # this rank's frames only
-            _, depth_m = self.core.estimate_depth(left_frame, right_frame)
+            _, depth_m = self.core.estimate_depth(left_frame, right_frame, **kw)
             yield depth_m
             if self._frame_interval > 0:
                 sleep_time = self._frame_interval - (time.time() - frame_start_time)
@@ -102,6 +107,7 @@ class StereoDepthEstimatorVideo:
 
         params = dict(self.core.get_sgbm_params())
         ds, fast = self.downscale_factor, self.fast_mode
+        scale = ds if self.device_downscale else None
 
         def make(dev):
             import torch
@@ -110,7 +116,7 @@ class StereoDepthEstimatorVideo:
             core.sgbm_params.update(params)
             core.sgbm_params['device'] = dev
             core._build_sgbm()
-            return DepthPipeline(core, dev, depth=3, streams=2)
+            return DepthPipeline(core, dev, depth=3, streams=2, input_scale=scale)
 
         frame_start_time = time.time()
         for depth_m in sharded_map(self._frames(), self.devices, make, queue_depth=4, pipelined=True):

@@ -38,7 +38,7 @@ EXPORTS = (
     "dsx_kernel_times", "dsx_reset_times", "dsx_workspace_bytes", "dsx_destroy", "dsx_last_error",
     "dsx_comm_init_all", "dsx_comm_size", "dsx_bcast", "dsx_comm_destroy",
     "dsx_fill_nearest_footprint", "dsx_fill_nearest_workspace_bytes", "dsx_fill_nearest_device",
-    "dsx_postprocess_device",
+    "dsx_postprocess_device", "dsx_resize_area_table", "dsx_resize_area_device",
 )
 
 
@@ -145,6 +145,8 @@ def _bind(lib):
         "dsx_postprocess_device": (ctypes.c_int, [vp, i32, i32, i64, i32, ctypes.POINTER(DsxPostParams), vp, vp, vp,
                                                    ctypes.c_size_t, vp]),
         "dsx_rectify_device": (ctypes.c_int, [vp, i32, i32, i64, i32, vp, vp, i32, i32, vp, vp]),
+        "dsx_resize_area_table": (ctypes.c_int, [i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]),
+        "dsx_resize_area_device": (ctypes.c_int, [vp, i32, i32, i64, i32, i32, i32, i32, vp, i64, vp]),
         "dsx_postprocess_fast_device": (ctypes.c_int, [vp, i32, i32, i64, i32, vp, vp, ctypes.c_double,
                                                         ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                                         ctypes.c_double, i32, vp]),

@@ -1044,6 +1044,38 @@ int dsx_rectify_device(const void *d_img, int32_t Hs, int32_t Ws, int64_t stride
     return DSX_OK;
 }
 
+int dsx_resize_area_table(int32_t in_size, int32_t out_size, int32_t *start, int32_t *count, int32_t *coef) {
+    g_err.clear();
+    if (!start || !count || !coef) return fail(DSX_EINVAL, "NULL table array");
+    if (out_size < 1 || out_size > in_size) return fail(DSX_EINVAL, "out_size must be in [1, in_size]");
+    if (dsx::resize_area_table(in_size, out_size, start, count, coef) != 0) return fail(DSX_EINVAL, "bad sizes");
+    return DSX_OK;
+}
+
+int dsx_resize_area_device(const void *d_img, int32_t Hs, int32_t Ws, int64_t stride_bytes, int32_t channels,
+                           int32_t Ho, int32_t Wo, int32_t gray_out, void *d_out, int64_t out_stride_bytes,
+                           void *hip_stream) {
+    g_err.clear();
+    if (!d_img || !d_out) return fail(DSX_EINVAL, "NULL image or output");
+    if (channels != 1 && channels != 3) return fail(DSX_EINVAL, "channels must be 1 or 3");
+    if (gray_out != 0 && gray_out != 1) return fail(DSX_EINVAL, "gray_out must be 0 or 1");
+    if (gray_out && channels != 3) return fail(DSX_EINVAL, "gray_out needs a 3-channel image");
+    if (Hs < 1 || Ws < 1 || Ho < 1 || Wo < 1) return fail(DSX_EINVAL, "sizes must be >= 1");
+    if (Ho > Hs || Wo > Ws) return fail(DSX_EINVAL, "the output must not be larger than the source (no upscaling)");
+    if (stride_bytes < (int64_t)Ws * channels) return fail(DSX_EINVAL, "stride_bytes must be >= Ws * channels");
+    if (out_stride_bytes < (int64_t)Wo * (gray_out ? 1 : channels))
+        return fail(DSX_EINVAL, "out_stride_bytes must be >= the output row");
+    if ((int64_t)Ws * channels > 0x7FFFFFFF || Ho > 4 * 65535) return fail(DSX_EINVAL, "image too large");
+    // the tables live on the image's device
+    hipPointerAttribute_t attr{};
+    if (hipPointerGetAttributes(&attr, d_img) == hipSuccess) DSX_HIP(hipSetDevice(attr.device));
+    else (void)hipGetLastError();
+    DSX_HIP(dsx::launch_resize_area(static_cast<const uint8_t *>(d_img), stride_bytes, Hs, Ws, channels, Ho, Wo,
+                                    gray_out != 0, static_cast<uint8_t *>(d_out), out_stride_bytes,
+                                    static_cast<hipStream_t>(hip_stream)));
+    return DSX_OK;
+}
+
 int dsx_compute_batch_device(dsx_handle *h, int32_t nframes, const void *dL, const void *dR, int64_t frame_stride_bytes,
                              int32_t H, int32_t W, int64_t stride_bytes, void *d_out_fixed, void *d_out_float,
                              void *hip_stream) {
@@ -1114,7 +1146,7 @@ int dsx_fill_holes_release(const void *d_workspace) {
 
 int dsx_shutdown(void) {
     g_err.clear();
-    if (!dsx::inpaint_has_words()) return DSX_OK;  // nothing kept: no HIP call (CPU-only hosts)
+    if (!dsx::inpaint_has_words() && !dsx::resize_has_tables()) return DSX_OK;  // nothing kept: no HIP call (CPU-only hosts)
     // the device may still write a workspace's mapped words: drain every device first.  (Freeing
     // them matters at exit: left to the HIP runtime's own teardown, the pinned mapped words were
     // the difference between a clean exit and a SIGSEGV inside libhsa-runtime64 under rocprofv3,
@@ -1128,6 +1160,7 @@ int dsx_shutdown(void) {
         (void)hipSetDevice(prev);
     }
     dsx::inpaint_forget_all();
+    dsx::resize_forget_all();
     return DSX_OK;
 }
 

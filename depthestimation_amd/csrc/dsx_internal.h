@@ -257,6 +257,17 @@ struct RectArgs {
 };
 hipError_t launch_rectify(const RectArgs &a, int channels, hipStream_t st);
 
+// Area downscale (dsx_resize.hip): input.py resize_area (Pillow BOX, two u8 passes) on the device.
+// (start, count, k) of each of the out_size outputs of one axis, in doubles on the host; -1 for
+// out_size < 1, out_size > in_size or a null array.  Host only: the one C home of the window rule.
+int resize_area_table(int in_size, int out_size, int32_t *start, int32_t *count, int32_t *coef);
+// One launch on the current device; the tables come from a library-owned cache (8 shapes per device),
+// uploaded on `st` at a shape's first use.  gray: 3 channels in, one gray byte per pixel out.
+hipError_t launch_resize_area(const uint8_t *img, int64_t stride, int Hs, int Ws, int channels, int Ho, int Wo,
+                              bool gray, uint8_t *out, int64_t out_stride, hipStream_t st);
+bool resize_has_tables();
+void resize_forget_all();  // frees every cached table (dsx_shutdown)
+
 
 
 }  // namespace dsx

@@ -39,6 +39,68 @@ def resize_area(img: np.ndarray, factor: float) -> np.ndarray:
     return np.asarray(Image.fromarray(img).resize(size, Image.BOX))
 
 
+def resize_area_table(in_size: int, out_size: int):
+    """(start, count, coef) int32 arrays of ``resize_area`` along one axis: output o averages the
+    ``count[o]`` input samples from ``start[o]`` as ``min(255, (2**21 + coef[o] * sum) >> 22)``.  Pillow's
+    BOX window rule in float64, restated; the C home of the same rule is dsx_resize_area_table
+    (include/dsx.h), whose tables the device kernel reads."""
+    in_size, out_size = int(in_size), int(out_size)
+    if out_size < 1 or out_size > in_size:
+        raise ValueError("out_size must be in [1, in_size]")
+    scale = in_size / out_size
+    fs = max(scale, 1.0)
+    sup, ss = 0.5 * fs, 1.0 / fs
+    start = np.zeros(out_size, np.int32)
+    count = np.zeros(out_size, np.int32)
+    coef = np.zeros(out_size, np.int32)
+    for o in range(out_size):
+        c = (o + 0.5) * scale
+        xmin = max(int(c - sup + 0.5), 0)
+        xmax = min(int(c + sup + 0.5), in_size)
+        taps = [x for x in range(xmin, xmax) if -0.5 < (x - c + 0.5) * ss <= 0.5]
+        start[o] = taps[0] if taps else xmin
+        count[o] = len(taps)
+        coef[o] = int((1.0 / len(taps)) * 4194304 + 0.5) if taps else 0
+    return start, count, coef
+
+
+def resize_area_device(img, factor: float, gray: bool = False, out=None, stream=None):
+    """``resize_area`` on the device (dsx_resize_area_device), bit for bit: ``img`` is a uint8 HIP tensor
+    H x W or H x W x 3 (unit element stride, any row stride), the result a uint8 HIP tensor of size
+    (int(H * factor), int(W * factor)).  ``gray`` (3 channels only): the H' x W' gray image
+    ``to_grayscale_bgr(resize_area(img))`` from the same launch.  ``out``: a uint8 tensor of the result's
+    shape with unit element stride.  Asynchronous on ``stream``; a zero output dimension raises ValueError
+    as Pillow does."""
+    import torch
+
+    from . import _dsx
+
+    if not hasattr(img, "is_cuda") or not img.is_cuda or img.dtype != torch.uint8 or img.dim() not in (2, 3):
+        raise ValueError("img must be a uint8 H x W (x 3) device tensor")
+    ch = 1 if img.dim() == 2 else img.shape[2]
+    if ch not in (1, 3) or img.stride(-1) != 1 or (img.dim() == 3 and img.stride(1) != ch):
+        raise ValueError("img must be gray or packed 3-channel with unit element stride")
+    if gray and ch != 3:
+        raise ValueError("gray=True needs a 3-channel image")
+    H, W = img.shape[0], img.shape[1]
+    Wo, Ho = int(W * factor), int(H * factor)
+    if Wo < 1 or Ho < 1:
+        raise ValueError("height and width must be > 0")
+    if Wo > W or Ho > H:
+        raise ValueError("resize_area_device only downscales (factor <= 1)")
+    shape = (Ho, Wo) if (gray or img.dim() == 2) else (Ho, Wo, ch)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=img.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != img.device or \
+            out.stride(-1) != 1 or (len(shape) == 3 and out.stride(1) != ch):
+        raise ValueError(f"out must be a uint8 tensor of shape {shape} on the input's device, unit element stride")
+    sptr = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
+    rc = _dsx.lib().dsx_resize_area_device(img.data_ptr(), H, W, img.stride(0), ch, Ho, Wo, int(bool(gray)),
+                                           out.data_ptr(), out.stride(0), sptr)
+    _dsx.check(rc, "dsx_resize_area_device")
+    return out
+
+
 def load_stereo_pair(left_image_path, right_image_path, downscale_factor=1.0):
     """input.py:9-45: RGB uint8 pair, optionally downscaled; FileNotFoundError if unreadable."""
     left = _imread_rgb(left_image_path)

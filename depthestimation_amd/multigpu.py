@@ -336,9 +336,11 @@ class DepthPipeline:
     pinned memory.  Frame i runs on stream i mod ``streams`` in ring slot i mod ``depth``; a push
     waits only on the frame that last used its slot.  ``push`` returns the completed frames'
     depth maps (numpy copies, None when focal length / baseline are unset - what the reference's
-    generator yields, StereoDepthEstimatorVideo.py:101-103)."""
+    generator yields, StereoDepthEstimatorVideo.py:101-103).  ``input_scale``: the pinned slots and the
+    uploads carry full-size frames and the input downscale (``input.resize_area_device``) runs on the
+    frame's stream, equal bit for bit to pushing ``resize_area`` of the frames."""
 
-    def __init__(self, core, device: int, depth: int = 3, streams: int = 2):
+    def __init__(self, core, device: int, depth: int = 3, streams: int = 2, input_scale=None):
         import copy
         import torch
         self.torch = torch
@@ -346,6 +348,7 @@ class DepthPipeline:
         self.dev = torch.device("cuda", int(device))
         torch.cuda.set_device(self.dev)
         self.depth = max(2, int(depth))
+        self.input_scale = input_scale
         self.streams = [torch.cuda.Stream(device=self.dev) for _ in range(max(1, int(streams)))]
         # one matcher handle per stream: a handle's scratch (the drop-in call's maps and workspace, LR
         # keys) orders its calls across streams, so a shared handle would run one frame at a time.  The
@@ -420,7 +423,8 @@ class DepthPipeline:
         with torch.cuda.stream(st):
             dl = hl.to(self.dev, non_blocking=True)
             dr = hr.to(self.dev, non_blocking=True)
-            _, z = core.estimate_depth_device(dl, dr, stream=st)
+            kw = {} if self.input_scale is None else {"input_scale": self.input_scale}
+            _, z = core.estimate_depth_device(dl, dr, stream=st, **kw)
             zshape = None
             if z is not None:
                 if self.hout[slot] is None or self.hout[slot].shape != z.shape:

@@ -43,6 +43,7 @@ from typing import Dict, Optional, Tuple
 
 import numpy as np
 
+from .input import resize_area, resize_area_device
 from .matcher import (HipBlockMatcher, default_workspace, fill_holes_status, postprocess_fast_device,
                       postprocess_full_device, rectify_device)
 from .postprocess import median_blur3, postprocess_disparity
@@ -271,11 +272,19 @@ class StereoCore:
             return rectify_device(left, m1L, m2L, stream=stream), rectify_device(right, m1R, m2R, stream=stream)
         return rectify_device(left, stream=stream), rectify_device(right, stream=stream)
 
-    def estimate_depth_device(self, left_source, right_source, stream=None):
+    def estimate_depth_device(self, left_source, right_source, stream=None, input_scale=None):
         """``estimate_depth`` (stereo_core.py:274-293) with every step on the device: raw uint8
-        HIP frames -> rectify / gray -> matcher -> crop + median (+ depth).  Returns HIP tensors."""
+        HIP frames -> rectify / gray -> matcher -> crop + median (+ depth).  Returns HIP tensors.
+
+        ``input_scale``: the frames arrive at full size and the input downscale (input.py:38-43,
+        ``resize_area``) runs on the device first, fused with the gray conversion for BGR frames - one
+        kernel instead of resize + gray; with a calibration the rectification then remaps the gray image.
+        Equal bit for bit to passing ``resize_area(frame, input_scale)``."""
         if left_source is None or right_source is None:
             raise ValueError("Left and right sources must be set before estimating depth.")
+        if input_scale is not None and input_scale != 1.0:
+            left_source = resize_area_device(left_source, input_scale, gray=left_source.dim() == 3, stream=stream)
+            right_source = resize_area_device(right_source, input_scale, gray=right_source.dim() == 3, stream=stream)
         self.left_rectified, self.right_rectified = self._prepare_rectified_device(left_source, right_source, stream)
         return self.process_pair_device(self.left_rectified, self.right_rectified, stream=stream)
 
@@ -329,19 +338,28 @@ class StereoCore:
             Z[Z > max_depth] = max_depth
         return Z
 
-    def estimate_depth(self, left_source, right_source) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+    def estimate_depth(self, left_source, right_source, input_scale=None) -> Tuple[np.ndarray, Optional[np.ndarray]]:
         """stereo_core.py:274-293.  Host arrays in, host arrays out; the work runs on the
         device pipeline (``estimate_depth_device``: rectify / gray, matcher, post-processing,
         depth, all in HBM - bit-identical to the host steps, tests/test_gpu_host_api.py) unless
-        the matcher was replaced."""
+        the matcher was replaced.
+
+        ``input_scale``: full-size frames in, downscaled by that factor on the device first
+        (``estimate_depth_device``); where the device pipeline does not apply to the downscaled shape,
+        the host ``resize_area`` and the host path run instead - the same result either way."""
         if left_source is None or right_source is None:
             raise ValueError("Left and right sources must be set before estimating depth.")
-        if self._device_pipeline_ok(left_source, right_source):
+        if input_scale is not None and input_scale == 1.0:
+            input_scale = None
+        if input_scale is not None and not self._device_pipeline_ok(left_source, right_source, input_scale):
+            return self.estimate_depth(resize_area(np.ascontiguousarray(left_source), input_scale),
+                                       resize_area(np.ascontiguousarray(right_source), input_scale))
+        if self._device_pipeline_ok(left_source, right_source, input_scale):
             import torch
             dev = torch.device("cuda", int(self.sgbm_params.get('device', 0)))
             tl = torch.from_numpy(np.require(left_source, requirements=('C', 'W'))).to(dev)
             tr = torch.from_numpy(np.require(right_source, requirements=('C', 'W'))).to(dev)
-            d, z = self.estimate_depth_device(tl, tr)
+            d, z = self.estimate_depth_device(tl, tr, input_scale=input_scale)
             self.left_rectified = _HostView(self.left_rectified)
             self.right_rectified = _HostView(self.right_rectified)
             self.disparity_map = d.cpu().numpy()
@@ -359,7 +377,7 @@ class StereoCore:
         if chk is not None:
             chk()
 
-    def _device_pipeline_ok(self, left, right) -> bool:
+    def _device_pipeline_ok(self, left, right, input_scale=None) -> bool:
         if 'compute_disparity' in self.__dict__:
             return False
         if not (isinstance(left, np.ndarray) and isinstance(right, np.ndarray)):
@@ -370,7 +388,9 @@ class StereoCore:
             return False
         p = self.sgbm_params
         if all(p.get(k) is not None for k in ('cam_matrix_L', 'cam_matrix_R', 'baseline', 'image_width', 'image_height')):
-            if tuple(left.shape[:2]) != (int(p['image_height']), int(p['image_width'])):
+            hw = tuple(left.shape[:2]) if input_scale is None else (int(left.shape[0] * input_scale),
+                                                                    int(left.shape[1] * input_scale))
+            if hw != (int(p['image_height']), int(p['image_width'])):
                 return False  # rectify_images' resize-on-mismatch path (rectify.py:92-105) is host-side
         try:
             import torch

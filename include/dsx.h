@@ -32,7 +32,8 @@
 extern "C" {
 #endif
 
-#define DSX_VERSION 106 /* additive since 1.0.6 (layouts unchanged): dsx_fill_nearest_*, dsx_postprocess_device,
+#define DSX_VERSION 106 /* additive since 1.0.6 (layouts unchanged): dsx_resize_area_*, dsx_fill_nearest_*,
+                           dsx_postprocess_device,
                            dsx_post_params.fill_method (a former reserved slot; 0 = as before);
                            1.0.6: hole filling in OpenCV's own arithmetic and exact queue order, dsx_fill_holes_release,
                            dsx_shutdown;
@@ -342,6 +343,32 @@ int dsx_postprocess_device(const void *d_disp, int32_t H, int32_t W, int64_t in_
 int dsx_rectify_device(const void *d_img, int32_t Hs, int32_t Ws, int64_t stride_bytes, int32_t channels,
                        const float *d_mapx, const float *d_mapy, int32_t H, int32_t W, void *d_out,
                        void *hip_stream);
+
+/* The input downscale on the device, replacing cv2.resize(INTER_AREA) of input.py:38-43,63-67 and
+ * threaded_stereo.py:45-47 in the arithmetic of this project's host step (input.py resize_area, Pillow's
+ * BOX resampling), bit for bit.  Per axis, input size I and output size O <= I:
+ *   scale = I / O, fs = max(scale, 1), sup = fs / 2, ss = 1 / fs (doubles);  output o has centre
+ *   c = (o + 0.5) scale and the taps x in [int(c - sup + 0.5), int(c + sup + 0.5)) clipped to [0, I) with
+ *   -0.5 < (x - c + 0.5) ss <= 0.5: `count` contiguous taps from `start`, coef k = int(2^22 / count + 0.5);
+ *   out = min(255, (2^21 + k * sum of the taps) >> 22).
+ * The horizontal pass runs first and rounds to uint8, the vertical pass runs on those values; an axis
+ * with O == I is the identity.
+ *
+ * dsx_resize_area_table (host only, no device): fills out_size entries of start / count / coef by the rule
+ *   above.  DSX_EINVAL for out_size < 1, out_size > in_size or a NULL array.
+ * dsx_resize_area_device: d_img uint8 Hs x Ws x channels (1 or 3), row stride `stride_bytes`; d_out uint8
+ *   Ho x Wo x channels with row stride `out_stride_bytes`, or with gray_out = 1 (channels = 3 only)
+ *   Ho x Wo gray: (c0 * 1868 + c1 * 9617 + c2 * 4899 + 8192) >> 14 of the rounded uint8 channel values,
+ *   the gray formula of dsx_rectify_device (resize, then gray).  1 <= Ho <= Hs, 1 <= Wo <= Ws (no
+ *   upscaling), Ho <= 262140.  One launch; integer arithmetic only on the device.  The tables of a
+ *   (Hs, Ws, Ho, Wo) are built on the host and kept by the library per device (8 shapes per device, the
+ *   least recently used dropped; freed by dsx_shutdown): a shape's first call uploads them on hip_stream
+ *   and waits for that copy, later calls allocate nothing and are asynchronous on hip_stream.
+ *   Thread-safe; runs on the device that owns d_img.  Argument errors are reported before any HIP call. */
+int dsx_resize_area_table(int32_t in_size, int32_t out_size, int32_t *start, int32_t *count, int32_t *coef);
+int dsx_resize_area_device(const void *d_img, int32_t Hs, int32_t Ws, int64_t stride_bytes, int32_t channels,
+                           int32_t Ho, int32_t Wo, int32_t gray_out, void *d_out, int64_t out_stride_bytes,
+                           void *hip_stream);
 
 /* Per-kernel timings accumulated since the last reset (params.timing = 1): names are
  * written as a ';'-separated list into `names` (capacity `names_cap`), average ms per
