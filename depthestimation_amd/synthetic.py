@@ -42,3 +42,30 @@ def stereo_pair(H: int, W: int, min_disp: int = 0, num_disp: int = 64, seed: int
     b = np.take_along_axis(R, np.clip(x0i + 1, 0, W - 1), 1).astype(np.float32)
     L = np.clip(np.rint(a * (1 - fr) + b * fr), 0, 255).astype(np.uint8)
     return L, R, d_gt
+
+
+def binary_pair(H: int, W: int, min_disp: int = 0, num_disp: int = 64, seed: int = 1234):
+    """``stereo_pair`` thresholded to {0, 255} (> 127 -> 255): every pixel difference is 0 or 255,
+    so block costs reach 255 * bs^2 and SGM path costs climb towards max cost + P2."""
+    L, R, d_gt = stereo_pair(H, W, min_disp, num_disp, seed=seed)
+    return _threshold(L), _threshold(R), d_gt
+
+
+STRIPE_COLS = 40
+
+
+def striped_pair(H: int, W: int, min_disp: int = 0, num_disp: int = 64, seed: int = 1234):
+    """``binary_pair`` whose first STRIPE_COLS columns hold period-2 vertical stripes (0, 255, 0,
+    255, ...) in both images (L == R there).  Inside the stripes every odd shift costs 255 * bs^2 and
+    every even shift 0 at every pixel (min_disp even), so with P1 = P2 the odd path costs grow by the
+    full block cost per step until they sit exactly on max cost + P2."""
+    L, R, d_gt = binary_pair(H, W, min_disp, num_disp, seed=seed)
+    n = min(STRIPE_COLS, W)
+    stripes = ((np.arange(n) & 1) * 255).astype(np.uint8)
+    L[:, :n] = stripes
+    R[:, :n] = stripes
+    return L, R, d_gt
+
+
+def _threshold(img: np.ndarray) -> np.ndarray:
+    return np.where(img > 127, 255, 0).astype(np.uint8)

@@ -36,6 +36,8 @@ def test_golden_sgm_fixtures():
         kw = dict(min_disp=int(z["min_disp"]), num_disp=int(z["num_disp"]), block_size=int(z["block_size"]),
                   mode=str(z["mode"]), uniqueness_ratio=int(z["uniqueness_ratio"]),
                   disp12_max_diff=int(z["disp12_max_diff"]), subpixel=bool(z["subpixel"]))
+        if "p1" in z.files:  # the saturated fixtures store their penalties; the others use the defaults
+            kw.update(P1=int(z["p1"]), P2=int(z["p2"]))
         got = stereo_sgm(z["L"], z["R"], **kw)
         np.testing.assert_array_equal(got["fixed"], z["fixed"], err_msg=os.path.basename(f))
 
@@ -145,10 +147,11 @@ def test_gpu_sgm_golden_fixtures():
     from depthestimation_amd.matcher import HipBlockMatcher
     for f in sorted(glob.glob(os.path.join(GOLDEN, "sgm_*.npz"))):
         z = np.load(f)
+        pen = dict(p1=int(z["p1"]), p2=int(z["p2"])) if "p1" in z.files else {}
         m = HipBlockMatcher(min_disp=int(z["min_disp"]), num_disp=int(z["num_disp"]), block_size=int(z["block_size"]),
                             cost="sad", uniqueness_ratio=int(z["uniqueness_ratio"]),
                             disp12_max_diff=int(z["disp12_max_diff"]), subpixel=bool(z["subpixel"]),
-                            aggregation=str(z["mode"]))
+                            aggregation=str(z["mode"]), **pen)
         np.testing.assert_array_equal(m.compute(z["L"], z["R"]), z["fixed"], err_msg=os.path.basename(f))
         m.close()
 
