@@ -35,6 +35,7 @@
 //                     pixel), checked afterwards by lr_fixup_sgbm
 #include "dsx_internal.h"
 #include "dsx_partition.h"
+#include "dsx_subpix.h"
 
 // Register budget (waves per SIMD) the fused pass is compiled for, measured per cost (r01e): SAD at 4
 // waves spills in the row loop (C2 +45 %); SSD blocks of >= 4 waves (D > 128) gain at 4 despite init
@@ -44,7 +45,17 @@ constexpr int kWpeSsd = 4;  // SSD blocks of >= 4 waves
 
 // Row-step forms that can be switched off for an A/B build (tools/variant_bm.sh -DDSX_ROWSTEP_ATID=0
 // / -DDSX_ROWSTEP_KEY2=0 / -DDSX_ROWSTEP_MERGE=0): the lane-indexed tile stores, the key-tree argmin and the
-// merged row staging of the pair layout.
+// merged row staging of the pair layout; -DDSX_ROWSTEP_DIVQ=0: the branch-free sub-pixel quotient of the left
+// tail.  -DDSX_ROWSTEP_PAIRTAIL=1 switches ON the left tail once per two rows, which is off by default: it issues
+// 2.7 % fewer VALU ops per C2 launch and ran 1 % slower than the build without it.
+#ifndef DSX_ROWSTEP_PAIRTAIL
+#define DSX_ROWSTEP_PAIRTAIL 0
+#endif
+#ifndef DSX_ROWSTEP_DIVQ
+#define DSX_ROWSTEP_DIVQ 1
+#endif
+constexpr bool kRowstepPairtail = DSX_ROWSTEP_PAIRTAIL;  // pair layout, one-wave left pass
+constexpr bool kRowstepDivq = DSX_ROWSTEP_DIVQ;          // pair layout, left pass
 #ifndef DSX_ROWSTEP_ATID
 #define DSX_ROWSTEP_ATID 1
 #endif
@@ -218,6 +229,9 @@ __device__ __forceinline__ uint32_t gmin(uint32_t v) {
 typedef const __attribute__((address_space(4))) uint32_t cu32;
 typedef const __attribute__((address_space(1))) uint8_t gu8;    // global memory, named for ld()
 typedef const __attribute__((address_space(1))) uint32_t gu32;
+typedef __attribute__((address_space(1))) uint8_t gw8;  // global memory, written
+typedef __attribute__((address_space(1))) int16_t g16;
+typedef __attribute__((address_space(1))) float gf32;
 
 // One segment: strip x0, rows [yb, ye). FAST: every staged search position lies inside the
 // image (one unaligned dword load per lane and row); otherwise replicate-clamped
@@ -706,6 +720,15 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
 
     // RL2: the lane's bytes in slot par ^ 2 of the first step
     uint32_t stg = (MRG ? m_lane : (uint32_t)(16 * tid)) + (uint32_t)((2 - (yb & 1) * 2) * SLOT);
+    // DIVQ: the left tail's sub-pixel quotient by subpix_quot (dsx_subpix.h) instead of div_trunc_small and its
+    // two divergent fix-up branches.
+    // PTAIL (pair layout, one-wave left pass; off by default, see DSX_ROWSTEP_PAIRTAIL): the epilogue's tail -
+    // valid band, sub-pixel step, output formation, the two global stores - serves one pixel per lane pair, so
+    // half of its issue slots repeat the other half.  With PTAIL it runs once per two rows, on 64 (row, pixel)
+    // outputs: the first row of a pair keeps its scan results in kp0 / kp1 across the next step.
+    constexpr bool PTAIL = kRowstepPairtail && !SSD && SIDE == 0 && NW == 1;
+    constexpr bool DIVQ = kRowstepDivq && !SSD && SIDE == 0;
+    uint32_t kp0 = 0, kp1 = 0;
     for (int y = yb; y < ye; ++y) {
         const Bm2Args &a = kargs_row<SIDE == 3>(a_in);
 #ifdef DSX_STAMPS
@@ -1192,6 +1215,62 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
                     const uint32_t real_max = padv < (1u << 24) ? padv : (1u << 24);
                     if (nm < real_max && nm * (uint32_t)(100 - a.uniq) < cb * 100u) valid = false;
                 }
+                if constexpr (PTAIL) {
+                    // Scan part, every row: what the tail needs of this row is (b, cb, valid, cm, cp), the same
+                    // in both lanes of the pixel, packed into two VGPRs.  The neighbour costs are read
+                    // unconditionally (b - 1 >= -1 and b + 1 <= Dp stay inside the block's LDS: the slot bytes
+                    // before the tile, the row's padding); the tail drops them where no sub-pixel step applies.
+                    const uint16_t *pc = reinterpret_cast<const uint16_t *>(tile + k * PITCH) + b;
+                    u16x2 mp;
+                    mp.x = pc[-1];
+                    mp.y = pc[1];
+                    const uint32_t c0 = (cb << 16) | ((uint32_t)valid << 15) | (uint32_t)b, c1 = as1(mp);
+                    // Tail part, once per two rows of the segment (paired by y - yb, so nothing is kept across
+                    // segments): on a pair's second row lane h = 0 finishes the kept row y - 1 and lane h = 1
+                    // row y; a segment's unpaired last row runs it on the h = 0 lanes alone.  Wave-uniform.
+                    int sec = (y - yb) & 1;
+                    asm("" : "+s"(sec));  // stays a scalar integer: left free it becomes a loop-carried lane mask
+                    const bool second = sec != 0;
+                    if (second || !more) {
+                        const bool prev = second && h == 0;
+                        const uint32_t s0 = prev ? kp0 : c0, s1 = prev ? kp1 : c1;
+                        const int tb = (int)(s0 & 0x7FFFu);
+                        const int32_t tcb = (int32_t)(s0 >> 16), cm = (int32_t)(s1 & 0xFFFFu), cp = (int32_t)(s1 >> 16);
+                        const bool tvalid = (s0 & 0x8000u) != 0;
+                        int32_t f = tb * 16;
+                        float pf = (float)(m + tb);
+                        if (a.subpix) {
+                            const bool sp = tb > 0 && tb < D - 1;
+                            int32_t den = cm + cp - 2 * tcb;
+                            den = den < 1 ? 1 : den;
+                            const int32_t num = (cm - cp) * 16 + den;
+                            const int32_t q = DIVQ ? subpix_quot(num, 2 * den) : div_trunc_small(num, 2 * den);
+                            f += sp ? q : 0;
+                            if (a.float_mode == 1 && sp) pf = (float)(m + tb) + (float)(cm - cp) / (float)(2 * den);
+                        }
+                        if ((second || h == 0) && x < W) {
+                            // one store writes two rows: the row base is wave-uniform (y - 1 on a second row,
+                            // pinned to SGPRs like the prefetch's row bases), the lane's part carries + W for h = 1
+                            long ro = fout + (long)(y - sec) * W;
+                            asm("" : "+s"(ro));
+                            const uint32_t xh = (uint32_t)(x + (h ? W : 0));
+                            const int16_t fx = tvalid ? (int16_t)(m * 16 + f) : (int16_t)((m - 1) * 16);
+                            if (a.out_fixed) {
+                                int16_t *rowp = a.out_fixed + ro;
+                                asm("" : "+s"(rowp));
+                                *(g16 *)((gw8 *)rowp + 2u * xh) = fx;
+                            }
+                            if (a.out_float) {
+                                float *rowp = a.out_float + ro;
+                                asm("" : "+s"(rowp));
+                                *(gf32 *)((gw8 *)rowp + 4u * xh) = a.float_mode == 0 ? (float)fx * 0.0625f : (tvalid ? pf : (float)(m - 1));
+                            }
+                        }
+                    } else {
+                        kp0 = c0;
+                        kp1 = c1;
+                    }
+                } else {
                 int32_t f = b * 16;
                 float pf = (float)(m + b);
                 if (a.subpix && b > 0 && b < D - 1) {
@@ -1206,7 +1285,8 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
                     }
                     int32_t den = cm + cp - 2 * (int32_t)cb;
                     den = den < 1 ? 1 : den;
-                    f += div_trunc_small((cm - cp) * 16 + den, 2 * den);
+                    if constexpr (DIVQ) f += subpix_quot((cm - cp) * 16 + den, 2 * den);
+                    else f += div_trunc_small((cm - cp) * 16 + den, 2 * den);
                     if (a.float_mode == 1) pf = (float)(m + b) + (float)(cm - cp) / (float)(2 * den);
                 }
                 if (h == 0 && x < W) {
@@ -1222,6 +1302,7 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
                     }
                     if (a.out_fixed) a.out_fixed[o] = fx;
                     if (a.out_float) a.out_float[o] = a.float_mode == 0 ? (float)fx * 0.0625f : (valid ? pf : (float)(m - 1));
+                }
                 }
             }
         }
