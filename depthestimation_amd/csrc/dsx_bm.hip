@@ -54,6 +54,16 @@ constexpr int kWpeSsd = 4;  // SSD blocks of >= 4 waves
 #ifndef DSX_ROWSTEP_DIVQ
 #define DSX_ROWSTEP_DIVQ 1
 #endif
+// -DDSX_ROWSTEP_OVERLAP=0 / -DDSX_ROWSTEP_AHEAD=0: the rotated row loop (row y - 1's epilogue issued between the
+// chunks of row y's column update) and the column update's LDS reads one chunk ahead (OVL / AHD in bm2_segment).
+#ifndef DSX_ROWSTEP_OVERLAP
+#define DSX_ROWSTEP_OVERLAP 1
+#endif
+#ifndef DSX_ROWSTEP_AHEAD
+#define DSX_ROWSTEP_AHEAD 1
+#endif
+constexpr bool kRowstepOverlap = DSX_ROWSTEP_OVERLAP;    // pair layout, one-wave left pass, R <= 5
+constexpr bool kRowstepAhead = DSX_ROWSTEP_AHEAD;        // pair layout, one-wave left pass, R <= 5
 constexpr bool kRowstepPairtail = DSX_ROWSTEP_PAIRTAIL;  // pair layout, one-wave left pass
 constexpr bool kRowstepDivq = DSX_ROWSTEP_DIVQ;          // pair layout, left pass
 #ifndef DSX_ROWSTEP_ATID
@@ -729,6 +739,121 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
     constexpr bool PTAIL = kRowstepPairtail && !SSD && SIDE == 0 && NW == 1;
     constexpr bool DIVQ = kRowstepDivq && !SSD && SIDE == 0;
     uint32_t kp0 = 0, kp1 = 0;
+    // OVL (pair layout, one-wave left pass, key argmin: R <= 5): the row loop rotated by half a step.  The
+    // epilogue of row y - 1 reads only the tile, the column update of row y only the staged slots and the
+    // column sums, and the tile is not rewritten before row y's box phase, so step y runs the two together:
+    // the epilogue is cut into stages at its dependent LDS reads (the eight block reads, the winning block, the
+    // two neighbour costs, the sub-pixel step) and stage s is issued in front of column chunk s, with one chunk
+    // of SADs between a read and its first use.  sched_barrier(0) pins the pieces in source order.  The stages
+    // are branch-free (the neighbour costs are read for every pixel, as in PTAIL, and dropped where no step
+    // applies); the wave-uniform uniqueness and parabola-float branches and the stores follow the last chunk.
+    // A segment's first step has no epilogue and one epilogue drains the segment behind its last step.
+    // AHD: chunk q + 1's LDS reads issued in front of chunk q's SADs, two register sets (only a step's first
+    // chunk waits).  Both forms take the column update in 4-column chunks, two sets of which hold what one
+    // 8-column chunk does.
+    constexpr bool CUQ = !SSD && SIDE == 0 && NW == 1 && R < 6 && kRowstepKey2 && !PTAIL;
+    constexpr bool OVL = kRowstepOverlap && CUQ, AHD = kRowstepAhead && CUQ;
+    constexpr int CQ = 4, NQ = (NC + CQ - 1) / CQ;
+    // Tile reads per stage and read stages: one read (4 VGPRs in flight) where the chunks suffice, two otherwise.
+    // With two, R = 4 and R = 5 spilled 8 B with both forms on; four overran the 168 VGPRs with OVL alone.
+    // Stages 0 .. NRS - 1 read, NRS block keys, NRS + 1 element keys, NRS + 2 sub-pixel step, NRS + 3 outputs.
+    constexpr int RPS = NQ >= 10 ? 1 : 2, NRS = 8 / RPS;
+    static_assert(NQ >= NRS + 2, "a column chunk per stage up to the element keys");
+    const int ek = tid / TPP, eh = tid % TPP, ex = x0 + ek;
+    const uint8_t *epx = tile + ek * PITCH + eh * DSL * CB;
+    uint4 etv[2] = {};
+    uint32_t ekmin = 0, ecb = 0, egblk = 0, ecm = 0, ecp = 0;
+    int eb = 0, ef = 0, eden = 1;
+    bool esp = false;
+    auto emin8 = [](uint4 v) __attribute__((always_inline)) -> uint32_t {
+        const u16x2 mm = __builtin_elementwise_min(__builtin_elementwise_min(as2(v.x), as2(v.y)),
+                                                   __builtin_elementwise_min(as2(v.z), as2(v.w)));
+        return umin2(mm.x, mm.y);
+    };
+    auto estage = [&](auto sc, int ey) __attribute__((always_inline)) {
+        constexpr int s = decltype(sc)::value;
+        static_assert(!OVL || (NB == 8 && TPP == 2), "overlapped epilogue: 64 disparities per lane, two lanes per pixel");
+        constexpr int GB = Dp / 8 <= 16 ? 4 : (Dp / 8 <= 32 ? 5 : 6);
+        if constexpr (s <= NRS) {  // RPS block reads per stage; the block keys (KEY2 of the sequential form) of those before
+            if constexpr (s == 0) ekmin = 0xFFFFFFFFu;
+#pragma unroll
+            for (int j = 0; j < (s > 0 ? RPS : 0); ++j) ekmin = umin2(ekmin, (emin8(etv[j]) << GB) | (uint32_t)(RPS * (s - 1) + j));
+            if constexpr (s < NRS) {
+#pragma unroll
+                for (int j = 0; j < RPS; ++j) etv[j] = *reinterpret_cast<const uint4 *>(epx + 16 * (RPS * s + j));
+            } else {  // the winning block and its read
+                const uint32_t kmin = gmin<TPP>(ekmin | (uint32_t)(eh * 8));
+                ecb = kmin >> GB;
+                egblk = kmin & ((1u << GB) - 1u);
+                etv[0] = *reinterpret_cast<const uint4 *>(epx + 16 * (egblk & 7u));
+            }
+        } else if constexpr (s == NRS + 1) {  // element keys, the winner, its neighbours' reads
+            const uint32_t w4[4] = {etv[0].x, etv[0].y, etv[0].z, etv[0].w};
+            uint32_t k8 = 0xFFFFFFFFu;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                k8 = umin2(k8, (w4[q] << 16) | (uint32_t)(2 * q));
+                k8 = umin2(k8, (w4[q] & 0xFFFF0000u) | (uint32_t)(2 * q + 1));
+            }
+            const uint32_t dl = (int)(egblk / 8) == eh ? egblk * 8 + (k8 & 7u) : 0xFFFFu;
+            eb = (int)gmin<TPP>(dl);
+            // b - 1 >= -1 and b + 1 <= Dp stay inside the block's LDS: the slot bytes before the tile, the row's padding
+            const uint16_t *pc = reinterpret_cast<const uint16_t *>(tile + ek * PITCH) + eb;
+            ecm = pc[-1];
+            ecp = pc[1];
+        } else if constexpr (s == NRS + 2) {  // sub-pixel step
+            esp = a.subpix && eb > 0 && eb < D - 1;
+            int32_t den = (int32_t)ecm + (int32_t)ecp - 2 * (int32_t)ecb;
+            eden = den < 1 ? 1 : den;
+            const int32_t num = ((int32_t)ecm - (int32_t)ecp) * 16 + eden;
+            const int32_t q = DIVQ ? subpix_quot(num, 2 * eden) : div_trunc_small(num, 2 * eden);
+            ef = eb * 16 + (esp ? q : 0);
+        } else {  // uniqueness, outputs
+            bool valid = ex < W && ex >= m + D - 1 && ex <= W - 1 + m;
+            if (a.uniq > 0) {
+                const int rel = eb - eh * DSL;
+                uint32_t nm = 0xFFFFFFFFu;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    // the block minima are not held across the column update (8 VGPRs): read again
+                    const bool hit = rel >= 8 * i - 1 && rel <= 8 * i + 8;
+                    nm = hit ? nm : umin2(nm, emin8(*reinterpret_cast<const uint4 *>(epx + 16 * i)));
+                }
+                const int ib0 = (rel - 1) >> 3, ib1 = (rel + 1) >> 3;
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    const int ib = t == 0 ? ib0 : ib1;
+                    if (ib >= 0 && ib < 8 && (t == 0 || ib1 != ib0)) {
+                        const uint4 v = *reinterpret_cast<const uint4 *>(epx + 16 * ib);
+                        const uint32_t c8[8] = {v.x & 0xFFFFu, v.x >> 16, v.y & 0xFFFFu, v.y >> 16,
+                                                v.z & 0xFFFFu, v.z >> 16, v.w & 0xFFFFu, v.w >> 16};
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) {
+                            const int dd = 8 * ib + e - rel;
+                            nm = (dd > 1 || dd < -1) ? umin2(nm, c8[e]) : nm;
+                        }
+                    }
+                }
+                nm = gmin<TPP>(nm);
+                const uint32_t real_max = padv < (1u << 24) ? padv : (1u << 24);
+                if (nm < real_max && nm * (uint32_t)(100 - a.uniq) < ecb * 100u) valid = false;
+            }
+            if (eh == 0 && ex < W) {
+                const long o = fout + (long)ey * W + ex;
+                const int16_t fx = valid ? (int16_t)(m * 16 + ef) : (int16_t)((m - 1) * 16);
+                if (a.out_fixed) a.out_fixed[o] = fx;
+                if (a.out_float) {
+                    if (a.float_mode == 0) {
+                        a.out_float[o] = (float)fx * 0.0625f;
+                    } else {
+                        float pf = (float)(m + eb);
+                        if (esp) pf = (float)(m + eb) + (float)((int32_t)ecm - (int32_t)ecp) / (float)(2 * eden);
+                        a.out_float[o] = valid ? pf : (float)(m - 1);
+                    }
+                }
+            }
+        }
+    };
     for (int y = yb; y < ye; ++y) {
         const Bm2Args &a = kargs_row<SIDE == 3>(a_in);
 #ifdef DSX_STAMPS
@@ -795,6 +920,74 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
                         cs[c0 + c] = __builtin_fmaf(-to, to, __builtin_fmaf(tn, tn, cs[c0 + c]));
                     }
                 }
+            }
+          }
+        } else if constexpr (OVL || AHD) {
+          if (y > yb) {
+            // this lane's staged words of chunk q (columns [CQ q, CQ q + CQ)), both slots: s_chunk / ref_chunk
+            // of the left form at the chunk width of this path
+            uint32_t sn[2][CQ + 1], so[2][CQ + 1], rn[2][CQ], ro[2][CQ];
+            uint32_t nxn = 0, nxo = 0;
+            auto rd = [&](auto qc) __attribute__((always_inline)) {
+                constexpr int q = decltype(qc)::value, c0 = CQ * q, t = AHD ? (q & 1) : 0;
+                const uint8_t *bn = (const uint8_t *)__builtin_assume_aligned(smem + par * SLOT + d0 * 4, 8);
+                const uint8_t *bo = (const uint8_t *)__builtin_assume_aligned(smem + (par + 1) * SLOT + d0 * 4, 8);
+                const uint4 vn = *reinterpret_cast<const uint4 *>(smem + par * SLOT + G::SROW + 4 * c0);
+                const uint4 vo = *reinterpret_cast<const uint4 *>(smem + (par + 1) * SLOT + G::SROW + 4 * c0);
+                rn[t][0] = vn.x; rn[t][1] = vn.y; rn[t][2] = vn.z; rn[t][3] = vn.w;
+                ro[t][0] = vo.x; ro[t][1] = vo.y; ro[t][2] = vo.z; ro[t][3] = vo.w;
+                sn[t][0] = c0 == 0 ? *reinterpret_cast<const uint32_t *>(bn + NC * 4) : nxn;
+                so[t][0] = c0 == 0 ? *reinterpret_cast<const uint32_t *>(bo + NC * 4) : nxo;
+#pragma unroll
+                for (int c = 1; c < CQ; c += 2) {
+                    if (c0 + c < NC) {
+                        const u32x2 pn = lds_read_b64(bn + (NC - 1 - c0 - c) * 4);
+                        const u32x2 po = lds_read_b64(bo + (NC - 1 - c0 - c) * 4);
+                        sn[t][c + 1] = pn.x; sn[t][c] = pn.y; nxn = pn.x;
+                        so[t][c + 1] = po.x; so[t][c] = po.y; nxo = po.x;
+                    }
+                }
+            };
+            auto sads = [&](auto qc) __attribute__((always_inline)) {
+                constexpr int q = decltype(qc)::value, c0 = CQ * q, t = AHD ? (q & 1) : 0;
+#pragma unroll
+                for (int c = 0; c < CQ; ++c) {
+                    if (c0 + c < NC) {
+                        const uint32_t en = sad_hi_u8(rn[t][c], sn[t][c], __builtin_amdgcn_sad_u8(rn[t][c], sn[t][c + 1], as1(cs[c0 + c])));
+                        const uint32_t lo = sad_hi_u8(ro[t][c], so[t][c], __builtin_amdgcn_sad_u8(ro[t][c], so[t][c + 1], 0u));
+                        // pinned to this chunk (in place, no instruction): left free, the SADs - pure values whose
+                        // next use is the box phase - are sunk behind the epilogue's branches, every staged
+                        // word of the step is then held across it, and the loop spills
+                        uint32_t v = en - lo;
+                        if constexpr (OVL) asm volatile("" : "+v"(v));
+                        cs[c0 + c] = as2(v);
+                    }
+                }
+            };
+            // epilogue stage q in front of chunk q
+            auto chunk = [&](auto qc) __attribute__((always_inline)) {
+                constexpr int q = decltype(qc)::value;
+                if constexpr (q < NQ) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (OVL && q < NRS + 3) estage(qc, y - 1);
+                    if constexpr (!AHD) rd(qc);
+                    else if constexpr (q + 1 < NQ) rd(std::integral_constant<int, q + 1>{});
+                    __builtin_amdgcn_sched_barrier(0);
+                    sads(qc);
+                }
+            };
+            if constexpr (AHD) rd(std::integral_constant<int, 0>{});
+            chunk(std::integral_constant<int, 0>{}); chunk(std::integral_constant<int, 1>{});
+            chunk(std::integral_constant<int, 2>{}); chunk(std::integral_constant<int, 3>{});
+            chunk(std::integral_constant<int, 4>{}); chunk(std::integral_constant<int, 5>{});
+            chunk(std::integral_constant<int, 6>{}); chunk(std::integral_constant<int, 7>{});
+            chunk(std::integral_constant<int, 8>{}); chunk(std::integral_constant<int, 9>{});
+            chunk(std::integral_constant<int, 10>{}); chunk(std::integral_constant<int, 11>{});
+            static_assert(NQ <= 12 && NQ >= 7, "chunks of the overlapped column update");
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (OVL) {
+                if constexpr (NQ < NRS + 3) estage(std::integral_constant<int, NRS + 2>{}, y - 1);
+                estage(std::integral_constant<int, NRS + 3>{}, y - 1);
             }
           }
         } else if (y > yb) {
@@ -1056,7 +1249,7 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
                     *reinterpret_cast<uint4 *>(reinterpret_cast<uint8_t *>(a.vol) + ((size_t)fout + (size_t)y * W + x) * (Dp * CB) + off) = v;
                 }
             }
-        } else {
+        } else if constexpr (!OVL) {
             // ---- epilogue: TPP lanes per pixel ----
             const int k = tid / TPP, h = tid % TPP;
             const int x = x0 + k;
@@ -1313,6 +1506,15 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
         DSX_STAMP(6);
         block_sync<NW>();
         DSX_STAMP(7);
+    }
+    if constexpr (OVL) {  // the segment's last row: nothing is kept across segments
+        auto dr = [&](auto sc) __attribute__((always_inline)) {
+            if constexpr (decltype(sc)::value <= NRS + 3) estage(sc, ye - 1);
+        };
+        dr(std::integral_constant<int, 0>{}); dr(std::integral_constant<int, 1>{}); dr(std::integral_constant<int, 2>{});
+        dr(std::integral_constant<int, 3>{}); dr(std::integral_constant<int, 4>{}); dr(std::integral_constant<int, 5>{});
+        dr(std::integral_constant<int, 6>{}); dr(std::integral_constant<int, 7>{}); dr(std::integral_constant<int, 8>{});
+        dr(std::integral_constant<int, 9>{}); dr(std::integral_constant<int, 10>{}); dr(std::integral_constant<int, 11>{});
     }
 }
 
