@@ -155,19 +155,27 @@ struct dsx_handle {
     hipEvent_t scratchDone = nullptr;
     hipStream_t scratchStream = nullptr;
     bool scratchPending = false;
+    // Every cached buffer carries the bytes it holds (0: not allocated).  ensure_buffers grows a
+    // buffer whose held size is below what the current parameters and shape need; dsx_workspace_bytes
+    // is the sum of these fields.
     uint8_t *dL = nullptr, *dR = nullptr;
     int16_t *dFixed = nullptr;
     float *dFloat = nullptr;
+    size_t stagingBytes = 0;     // dL + dR + dFixed + dFloat (dsx_compute_host)
     uint32_t *lrKeys = nullptr;  // LR check: right-view winner keys per pixel (atomicMin target)
     int16_t *dStar = nullptr;    // LR check: left winners (or -1) for lr_fixup
+    size_t lrKeysBytes = 0, dStarBytes = 0;
     void *vol = nullptr;
     size_t vol_bytes = 0;
     void *btWs = nullptr;  // DSX_COST_BT: prep records of both views | horizontal sums
+    size_t btWsBytes = 0;
     int16_t *postIn = nullptr;  // sgbm_post: the matcher's int16 maps (postFrames frames)
     void *postWs = nullptr;     // sgbm_post: median | speckle components
+    size_t postInBytes = 0, postWsBytes = 0;
     int postFrames = 0;
     float *ppDisp = nullptr;    // dsx_process_pair_device: the matcher's float map (H x W, fast mode)
     int16_t *ppFixed = nullptr; // dsx_process_pair_device: the matcher's x16 map (H x W, full mode)
+    size_t ppDispBytes = 0, ppFixedBytes = 0;
     const uint32_t *lastKeys = nullptr;  // the last fused call's LR key half (run, defer_lr)
     const int16_t *lastDstar = nullptr;
     int lastKshift = 0;
@@ -175,6 +183,7 @@ struct dsx_handle {
     size_t ppWsBytes = 0;
     uint32_t *sgmS = nullptr;  // SGM path sums [H][W][Dp] u32 (sequential directions)
     uint16_t *sgmL = nullptr;  // SGM L_r per direction, ndir x [H][W][Dp] u16 (concurrent directions)
+    size_t sgmSBytes = 0, sgmLBytes = 0;  // sgmL follows the direction count of the aggregation mode
     // timing
     std::vector<std::string> knames;
     std::vector<double> ktotal;
@@ -218,6 +227,8 @@ void free_buffers(dsx_handle *h) {
     h->dStar = nullptr;
     h->vol = nullptr;
     h->vol_bytes = 0;
+    h->stagingBytes = h->lrKeysBytes = h->dStarBytes = h->btWsBytes = h->postInBytes = h->postWsBytes = 0;
+    h->ppDispBytes = h->ppFixedBytes = h->sgmSBytes = h->sgmLBytes = 0;
     h->cH = h->cW = h->cDp = h->cCostBytes = 0;
     h->lrFrames = 0;
     h->lrDirty[0] = h->lrDirty[1] = 0;
@@ -238,6 +249,19 @@ bool sgm_concurrent(const dsx_handle *h) {
     return !seq && max_cost(h->p) + (uint64_t)sgm_p2(h) < 0xFFFFull;
 }
 
+// Grows a cached buffer to at least `need` bytes (it may stay larger; the contents are scratch and
+// are not kept).  hipFree waits for the device, so no earlier launch still uses the old block.
+template <class T>
+int grow(T *&buf, size_t &held, size_t need) {
+    if (held >= need) return DSX_OK;
+    (void)hipFree(buf);
+    buf = nullptr;
+    held = 0;
+    DSX_HIP(hipMalloc(&buf, need));
+    held = need;
+    return DSX_OK;
+}
+
 int ensure_buffers(dsx_handle *h, int H, int W, bool host_staging, int nframes = 1) {
     const int cbytes = h->p.cost == DSX_COST_SSD ? 4 : 2;
     if (h->cH != H || h->cW != W || h->cDp != h->g.Dp || h->cCostBytes != cbytes) free_buffers(h);
@@ -248,6 +272,7 @@ int ensure_buffers(dsx_handle *h, int H, int W, bool host_staging, int nframes =
         DSX_HIP(hipMalloc(&h->dR, n));
         DSX_HIP(hipMalloc(&h->dFixed, n * 2));
         DSX_HIP(hipMalloc(&h->dFloat, n * 4));
+        h->stagingBytes = n * (1 + 1 + 2 + 4);
     }
     const bool fused = h->p.path == DSX_PATH_FUSED && !h->p.aggregation && h->p.cost != DSX_COST_BT;
     const bool lr_any = h->p.disp12_max_diff >= 0 || h->p.lr_form == DSX_LR_FORM_SGBM;  // OpenCV's form: always on
@@ -257,8 +282,11 @@ int ensure_buffers(dsx_handle *h, int H, int W, bool host_staging, int nframes =
         h->lrKeys = nullptr;
         h->dStar = nullptr;
         h->lrFrames = 0;
+        h->lrKeysBytes = h->dStarBytes = 0;
         DSX_HIP(hipMalloc(&h->lrKeys, 2 * n * nframes * 4));  // two halves: this frame / next frame
+        h->lrKeysBytes = 2 * n * nframes * 4;
         DSX_HIP(hipMalloc(&h->dStar, n * nframes * 2));
+        h->dStarBytes = n * nframes * 2;
         // lr_fixup restores ~0 after every frame.  The handle's streams are non-blocking, so the
         // fill must have landed before any later launch: wait for it here (allocation time only)
         DSX_HIP(hipMemsetAsync(h->lrKeys, 0xFF, 2 * n * nframes * 4, nullptr));
@@ -269,26 +297,28 @@ int ensure_buffers(dsx_handle *h, int H, int W, bool host_staging, int nframes =
     }
 
     const bool bt = h->p.cost == DSX_COST_BT;
-    if (!fused && !h->vol) {
-        h->vol_bytes = n * h->g.Dp * cbytes;
-        DSX_HIP(hipMalloc(&h->vol, h->vol_bytes));
-    }
-    if (bt && !h->btWs) DSX_HIP(hipMalloc(&h->btWs, dsx::bt_workspace(H, W, h->g.Dp)));
+    int rc = DSX_OK;
+    if (!fused && (rc = grow(h->vol, h->vol_bytes, n * h->g.Dp * cbytes))) return rc;
+    if (bt && (rc = grow(h->btWs, h->btWsBytes, dsx::bt_workspace(H, W, h->g.Dp)))) return rc;
     if (h->p.sgbm_post && h->postFrames < nframes) {
         (void)hipFree(h->postIn);
         h->postIn = nullptr;
         h->postFrames = 0;
+        h->postInBytes = 0;
         DSX_HIP(hipMalloc(&h->postIn, n * nframes * 2));
+        h->postInBytes = n * nframes * 2;
         h->postFrames = nframes;
     }
-    if (h->p.sgbm_post && !h->postWs) DSX_HIP(hipMalloc(&h->postWs, dsx::sgbm_post_workspace(H, W)));
+    if (h->p.sgbm_post && (rc = grow(h->postWs, h->postWsBytes, dsx::sgbm_post_workspace(H, W)))) return rc;
     if (h->p.aggregation) {
         if (sgm_concurrent(h)) {
+            // one u16 plane set per direction: the buffer follows the mode's direction count
+            // (sgm_paths_all writes L + dir * lstride for every dir below nd)
             const int *set;
             const int nd = sgm_set(h->p.aggregation, &set);
-            if (!h->sgmL) DSX_HIP(hipMalloc(&h->sgmL, (size_t)nd * n * h->g.Dp * 2));
-        } else if (!h->sgmS) {
-            DSX_HIP(hipMalloc(&h->sgmS, n * h->g.Dp * 4));
+            if ((rc = grow(h->sgmL, h->sgmLBytes, (size_t)nd * n * h->g.Dp * 2))) return rc;
+        } else if ((rc = grow(h->sgmS, h->sgmSBytes, n * h->g.Dp * 4))) {
+            return rc;
         }
     }
     h->cH = H;
@@ -803,9 +833,9 @@ int dsx_create(int device, const dsx_params *p, dsx_handle **out) {
 
 int dsx_set_params(dsx_handle *h, const dsx_params *p) {
     g_err.clear();
-    if (!h) return fail(DSX_EINVAL, "handle is NULL");
-    int rc = check(p);
+    int rc = check(p);  // first: a rejected set reports its own cause, whatever the handle
     if (rc) return rc;
+    if (!h) return fail(DSX_EINVAL, "handle is NULL");
     DSX_HIP(hipSetDevice(h->device));
     DSX_HIP(hipStreamSynchronize(h->stream));
     h->p = *p;
@@ -1209,8 +1239,8 @@ int dsx_process_pair_device(dsx_handle *h, const void *dL, const void *dR, int32
     if (rc) return rc;
     const size_t n = (size_t)H * W;
     const bool full = pp->mode == DSX_POST_FULL;
-    if (!full && !h->ppDisp) DSX_HIP(hipMalloc(&h->ppDisp, n * 4));
-    if (full && !h->ppFixed) DSX_HIP(hipMalloc(&h->ppFixed, n * 2));
+    if (!full && (rc = grow(h->ppDisp, h->ppDispBytes, n * 4))) return rc;
+    if (full && (rc = grow(h->ppFixed, h->ppFixedBytes, n * 2))) return rc;
     const size_t wsb = dsx::post_full_workspace(H, W, crop);
     if (pp->mode == DSX_POST_FULL && h->ppWsBytes < wsb) {
         (void)hipFree(h->ppWs);
@@ -1331,12 +1361,9 @@ int dsx_reset_times(dsx_handle *h) {
 
 int dsx_workspace_bytes(dsx_handle *h, int64_t *bytes) {
     if (!h || !bytes) return fail(DSX_EINVAL, "NULL argument");
-    const int64_t n = (int64_t)h->cH * h->cW;
-    int64_t b = 0;
-    if (h->dL) b += n * (1 + 1 + 2 + 4);
-    if (h->lrKeys) b += n * 10 * h->lrFrames;
-    b += (int64_t)h->vol_bytes;
-    *bytes = b;
+    *bytes = (int64_t)(h->stagingBytes + h->lrKeysBytes + h->dStarBytes + h->vol_bytes + h->btWsBytes +
+                       h->postInBytes + h->postWsBytes + h->sgmSBytes + h->sgmLBytes + h->ppDispBytes +
+                       h->ppFixedBytes + h->ppWsBytes);
     return DSX_OK;
 }
 

@@ -128,6 +128,27 @@ class HipBlockMatcher:
     def params(self) -> dict:
         return dict(self._cfg)
 
+    def set_params(self, **kw):
+        """Replace parameters of this matcher (dsx_set_params; configure_sgbm -> _build_sgbm,
+        stereo_core.py:77-123): ``kw`` is merged into ``params``, validated on the host like the
+        constructor does, and handed to the existing handle, which keeps its cached buffers and grows
+        them on the next call where needed.  With no handle yet the set is only stored.  Any error
+        raises ValueError and leaves the matcher as it was.  ``device`` cannot change."""
+        unknown = sorted(set(kw) - set(self._cfg))
+        if unknown:
+            raise ValueError(f"set_params: unknown parameter(s) {unknown}; known: {sorted(self._cfg)}")
+        cfg = dict(self._cfg, **kw)
+        try:
+            params = _dsx.make_params(**cfg)
+        except (TypeError, OverflowError) as e:
+            raise ValueError(f"set_params: {e}") from e
+        _dsx.check_params(params)
+        if self._h is not None:
+            rc = _dsx.lib().dsx_set_params(self._h, ctypes.byref(params))
+            if rc != _dsx.DSX_OK:
+                raise ValueError(f"dsx_set_params: {_dsx.last_error() or 'error ' + str(rc)}")
+        self._params, self._cfg = params, cfg
+
     # -- cv2.StereoMatcher-style getters (cv2 names used by depthlib docs) --------------------
     def getMinDisparity(self):
         return self._cfg["min_disp"]

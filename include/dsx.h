@@ -135,7 +135,9 @@ int dsx_check_params(const dsx_params *p);
 int dsx_create(int device, const dsx_params *p, dsx_handle **out);
 
 /* Replace the parameters of an existing matcher (configure_sgbm -> _build_sgbm,
- * stereo_core.py:77-123). Cached device buffers are invalidated when sizes change. */
+ * stereo_core.py:77-123). The parameters are validated first (DSX_EINVAL names the cause and the
+ * handle keeps its old set). The next call grows every cached device buffer that the new set needs
+ * larger (e.g. the SGM buffer with the direction count); a buffer may stay larger than needed. */
 int dsx_set_params(dsx_handle *h, const dsx_params *p);
 
 /* Synchronous host-buffer compute (replaces matcher.compute, stereo_core.py:231).
@@ -377,7 +379,10 @@ int dsx_kernel_times(dsx_handle *h, char *names, int names_cap, float *ms, int *
                      int *n);
 int dsx_reset_times(dsx_handle *h);
 
-/* Device bytes currently held by the handle's buffer cache. */
+/* Device bytes currently held by the handle's buffer cache: the host-call staging images and
+ * outputs, the LR keys and left winners, the cost volume, the BT records, the SGM sums of either
+ * form, the sgbm_post input and workspace, and dsx_process_pair_device's maps and workspace.
+ * Buffers kept from an earlier parameter set count until a shape or geometry change frees them. */
 int dsx_workspace_bytes(dsx_handle *h, int64_t *bytes);
 
 /* Destroy the matcher and free its device buffers. */
