@@ -39,6 +39,8 @@ EXPORTS = (
     "dsx_comm_init_all", "dsx_comm_size", "dsx_bcast", "dsx_comm_destroy",
     "dsx_fill_nearest_footprint", "dsx_fill_nearest_workspace_bytes", "dsx_fill_nearest_device",
     "dsx_postprocess_device", "dsx_resize_area_table", "dsx_resize_area_device",
+    "dsx_default_prefilter", "dsx_check_prefilter", "dsx_set_prefilter", "dsx_prefilter_device",
+    "dsx_texture_sum_device",
 )
 
 
@@ -68,6 +70,20 @@ class DsxParams(ctypes.Structure):
         ("lr_form", ctypes.c_int32),
         ("in_flight", ctypes.c_int32),
         ("reserved", ctypes.c_int32 * 2),
+    ]
+
+
+PREFILTER = {"none": 0, "xsobel": 1, "mean": 2}  # DSX_PREFILTER_* (include/dsx.h)
+
+
+class DsxPrefilter(ctypes.Structure):
+    """dsx_prefilter (include/dsx.h): the matcher prefilter and the texture threshold."""
+    _fields_ = [
+        ("type", ctypes.c_int32),
+        ("size", ctypes.c_int32),
+        ("cap", ctypes.c_int32),
+        ("texture_threshold", ctypes.c_int32),
+        ("reserved", ctypes.c_int32 * 4),
     ]
 
 
@@ -117,7 +133,13 @@ _lock = threading.Lock()
 def _bind(lib):
     vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
     P = ctypes.POINTER(DsxParams)
+    F = ctypes.POINTER(DsxPrefilter)
     sig = {
+        "dsx_default_prefilter": (None, [F]),
+        "dsx_check_prefilter": (ctypes.c_int, [P, F]),
+        "dsx_set_prefilter": (ctypes.c_int, [vp, F]),
+        "dsx_prefilter_device": (ctypes.c_int, [vp, i32, i32, i64, F, vp, i64, vp]),
+        "dsx_texture_sum_device": (ctypes.c_int, [vp, i32, i32, i64, i32, i32, vp, vp]),
         "dsx_version": (ctypes.c_int, []),
         "dsx_device_count": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)]),
         "dsx_default_params": (None, [P]),
@@ -258,6 +280,23 @@ def make_params(min_disp=0, num_disp=128, block_size=5, cost="sad", uniqueness_r
     p.lr_form = LR_FORM[lr_form]
     p.in_flight = int(bool(in_flight))
     return p
+
+
+def make_prefilter(prefilter_type="none", prefilter_size=9, prefilter_cap=31, texture_threshold=0) -> DsxPrefilter:
+    f = DsxPrefilter()
+    lib().dsx_default_prefilter(ctypes.byref(f))
+    if prefilter_type not in PREFILTER:
+        raise ValueError(f"prefilter_type must be one of {list(PREFILTER)}")
+    f.type = PREFILTER[prefilter_type]
+    f.size = int(prefilter_size)
+    f.cap = int(prefilter_cap)
+    f.texture_threshold = int(texture_threshold)
+    return f
+
+
+def check_prefilter(p, f: DsxPrefilter) -> None:
+    """Validate a prefilter against matcher parameters (``p`` None: the filter's own ranges)."""
+    check(lib().dsx_check_prefilter(None if p is None else ctypes.byref(p), ctypes.byref(f)), "dsx_check_prefilter")
 
 
 def check_params(p: DsxParams) -> None:

@@ -131,6 +131,26 @@ int check(const dsx_params *p) {
     return DSX_OK;
 }
 
+// p may be NULL (the filter's own ranges only)
+int check_prefilter(const dsx_params *p, const dsx_prefilter *f) {
+    if (!f) return fail(DSX_EINVAL, "prefilter is NULL");
+    if (f->type != DSX_PREFILTER_NONE && f->type != DSX_PREFILTER_XSOBEL && f->type != DSX_PREFILTER_MEAN)
+        return fail(DSX_EINVAL, "prefilter type must be NONE (0), XSOBEL (1) or MEAN (2)");
+    if (f->texture_threshold < 0 || f->texture_threshold > 65535)
+        return fail(DSX_EINVAL, "texture_threshold must be in [0, 65535]");
+    if (f->type == DSX_PREFILTER_NONE) {
+        if (f->texture_threshold > 0)
+            return fail(DSX_EINVAL, "texture_threshold > 0 needs a prefilter (the cap has no meaning on raw images)");
+        return DSX_OK;
+    }
+    if (f->size < 5 || f->size > 21 || (f->size & 1) == 0)
+        return fail(DSX_EINVAL, "prefilter size must be odd and in [5, 21]");
+    if (f->cap < 1 || f->cap > 63) return fail(DSX_EINVAL, "prefilter cap must be in [1, 63]");
+    if (p && p->cost == DSX_COST_BT)
+        return fail(DSX_EINVAL, "cost BT filters for itself: it cannot be combined with a prefilter");
+    return DSX_OK;
+}
+
 struct TimedLaunch {
     int kernel;
     hipEvent_t a, b;
@@ -141,6 +161,7 @@ struct TimedLaunch {
 struct dsx_handle {
     int device = 0;
     dsx_params p{};
+    dsx_prefilter pf{};  // type NONE: no filter, no mask, no buffer
     dsx::Geometry g{};
     hipStream_t stream = nullptr;  // for dsx_compute_host
     // buffer cache keyed by (H, W, geometry); single entry like RectificationCache (rectify.py:49-50)
@@ -151,7 +172,7 @@ struct dsx_handle {
     // Handle-owned scratch (LR keys / left winners, cost volume, BT records, SGM sums, the
     // sgbm_post input and workspace) is reused by every call: a call that touches it on another
     // stream than the previous such call waits for that call's last kernel (event) first.  Only
-    // the plain fused pass (no LR check, no sgbm_post) owns no scratch and runs unordered.
+    // the plain fused pass (no LR check, no sgbm_post, no prefilter) owns no scratch and runs unordered.
     hipEvent_t scratchDone = nullptr;
     hipStream_t scratchStream = nullptr;
     bool scratchPending = false;
@@ -162,6 +183,8 @@ struct dsx_handle {
     int16_t *dFixed = nullptr;
     float *dFloat = nullptr;
     size_t stagingBytes = 0;     // dL + dR + dFixed + dFloat (dsx_compute_host)
+    uint8_t *pfBuf = nullptr;    // prefilter: the filtered left views of every frame, then the right views
+    size_t pfBytes = 0;          //   (rows pf_pitch(W) apart)
     uint32_t *lrKeys = nullptr;  // LR check: right-view winner keys per pixel (atomicMin target)
     int16_t *dStar = nullptr;    // LR check: left winners (or -1) for lr_fixup
     size_t lrKeysBytes = 0, dStarBytes = 0;
@@ -199,6 +222,9 @@ void free_buffers(dsx_handle *h) {
     (void)hipFree(h->dR);
     (void)hipFree(h->dFixed);
     (void)hipFree(h->dFloat);
+    (void)hipFree(h->pfBuf);
+    h->pfBuf = nullptr;
+    h->pfBytes = 0;
     (void)hipFree(h->lrKeys);
     (void)hipFree(h->dStar);
     (void)hipFree(h->vol);
@@ -251,6 +277,9 @@ bool sgm_concurrent(const dsx_handle *h) {
 
 // Grows a cached buffer to at least `need` bytes (it may stay larger; the contents are scratch and
 // are not kept).  hipFree waits for the device, so no earlier launch still uses the old block.
+// Row pitch of the filtered images: whole 16-B groups, so every row takes the wide stores.
+int64_t pf_pitch(int W) { return ((int64_t)W + 15) & ~(int64_t)15; }
+
 template <class T>
 int grow(T *&buf, size_t &held, size_t need) {
     if (held >= need) return DSX_OK;
@@ -298,6 +327,9 @@ int ensure_buffers(dsx_handle *h, int H, int W, bool host_staging, int nframes =
 
     const bool bt = h->p.cost == DSX_COST_BT;
     int rc = DSX_OK;
+    if (h->pf.type != DSX_PREFILTER_NONE &&
+        (rc = grow(h->pfBuf, h->pfBytes, 2 * (size_t)nframes * H * (size_t)pf_pitch(W))))
+        return rc;
     if (!fused && (rc = grow(h->vol, h->vol_bytes, n * h->g.Dp * cbytes))) return rc;
     if (bt && (rc = grow(h->btWs, h->btWsBytes, dsx::bt_workspace(H, W, h->g.Dp)))) return rc;
     if (h->p.sgbm_post && h->postFrames < nframes) {
@@ -513,9 +545,54 @@ int check_fill_shape(int64_t H, int64_t W) {
     return DSX_OK;
 }
 
+// Orders a call that touches handle scratch on `st` after the previous such call on another stream.
+int wait_scratch(dsx_handle *h, hipStream_t st) {
+    if (h->scratchPending && h->scratchStream != st) DSX_HIP(hipStreamWaitEvent(st, h->scratchDone, 0));
+    return DSX_OK;
+}
+
+// Filters both views of every frame into the handle's buffers (one launch) and redirects the inputs
+// to them: the passes that follow read the filtered images like any caller's.
+int run_prefilter(dsx_handle *h, const void *&dL, const void *&dR, int H, int W, int64_t &stride, hipStream_t st,
+                  int nframes, int64_t &frame_stride) {
+    const int64_t P = pf_pitch(W);
+    dsx::PrefilterArgs a{};
+    a.src[0] = static_cast<const uint8_t *>(dL);
+    a.src[1] = static_cast<const uint8_t *>(dR);
+    a.stride = stride;
+    a.frame_stride = nframes > 1 ? frame_stride : 0;
+    a.dst[0] = h->pfBuf;
+    a.dst[1] = h->pfBuf + (size_t)nframes * H * P;
+    a.dpitch = P;
+    a.dframe = (int64_t)H * P;
+    a.dwidth = (int)P;
+    a.nviews = 2;
+    a.nframes = nframes;
+    a.H = H;
+    a.W = W;
+    a.type = h->pf.type;
+    a.n = h->pf.size;
+    a.cap = h->pf.cap;
+    DSX_LAUNCH(h, "prefilter", st, dsx::launch_prefilter(a, st));
+    dL = a.dst[0];
+    dR = a.dst[1];
+    stride = P;
+    frame_stride = a.dframe;
+    return DSX_OK;
+}
+
 int run_right_pass(dsx_handle *h, const void *dL, const void *dR, int H, int W, int64_t stride, int16_t *out,
                    hipStream_t st) {
     if (h->p.cost == DSX_COST_BT) return fail(DSX_EINVAL, "the right-view map is a block-matching (SAD/SSD) pass");
+    const bool pf = h->pf.type != DSX_PREFILTER_NONE;
+    ScratchRecord rec_(h, st, false);
+    if (pf) {
+        int rc = wait_scratch(h, st);
+        if (rc) return rc;
+        rec_.active = true;
+        int64_t fs = 0;
+        if ((rc = run_prefilter(h, dL, dR, H, W, stride, st, 1, fs))) return rc;
+    }
     dsx::Bm2Args a = base_args(h, H, W, stride);
     a.side = dsx::SIDE_RIGHT;
     a.ref = static_cast<const uint8_t *>(dR);
@@ -523,7 +600,7 @@ int run_right_pass(dsx_handle *h, const void *dL, const void *dR, int H, int W, 
     a.out_dR = out;
     const int radius = h->p.block_size / 2;
     DSX_LAUNCH(h, "bm_pass_right", st, dsx::launch_bm2(radius, h->g.kind, h->g.NW, a, st));
-    return DSX_OK;
+    return rec_.finish();
 }
 
 // nframes frames: inputs frame_stride bytes apart, outputs (and LR buffers) H * W elements apart
@@ -539,12 +616,22 @@ int run(dsx_handle *h, const void *dL, const void *dR, int H, int W, int64_t str
     void *const finalFixed = outFixed, *const finalFloat = outFloat;
     const bool fused = h->p.path == DSX_PATH_FUSED && !h->p.aggregation && !bt;
     const bool lr_sg = h->p.lr_form == DSX_LR_FORM_SGBM;  // OpenCV's LR form (always on)
-    const bool scratch = h->p.disp12_max_diff >= 0 || lr_sg || !fused || h->p.sgbm_post;
-    if (scratch && h->scratchPending && h->scratchStream != st) DSX_HIP(hipStreamWaitEvent(st, h->scratchDone, 0));
+    const bool pf = h->pf.type != DSX_PREFILTER_NONE;  // the filtered images are handle scratch too
+    const bool scratch = h->p.disp12_max_diff >= 0 || lr_sg || !fused || h->p.sgbm_post || pf;
+    if (scratch) {
+        int rc = wait_scratch(h, st);
+        if (rc) return rc;
+    }
     ScratchRecord rec_(h, st, scratch);  // on every exit once launches may have been enqueued
     if (h->p.sgbm_post) {
         outFixed = h->postIn;
         outFloat = nullptr;
+    }
+    const uint8_t *texL = nullptr;  // the filtered left views, for the texture mask
+    if (pf) {
+        int rc = run_prefilter(h, dL, dR, H, W, stride, st, nframes, frame_stride);
+        if (rc) return rc;
+        texL = static_cast<const uint8_t *>(dL);
     }
     if (fused) {
         const bool lr = h->p.disp12_max_diff >= 0 && !lr_sg;
@@ -735,6 +822,24 @@ int run(dsx_handle *h, const void *dL, const void *dR, int H, int W, int64_t str
             DSX_LAUNCH(h, "volume_wta", st, dsx::launch_volume_wta(h->g.TX, wide, v, st));
         }
     }
+    if (pf && h->pf.texture_threshold > 0) {
+        // after the last matcher kernel (uniqueness, sub-pixel, LR check), before the sgbm_post tail
+        dsx::TextureArgs t{};
+        t.pref = texL;
+        t.stride = stride;
+        t.frame_stride = frame_stride;
+        t.nframes = nframes;
+        t.H = H;
+        t.W = W;
+        t.block = h->p.block_size;
+        t.cap = h->pf.cap;
+        t.thr = h->pf.texture_threshold;
+        t.out_fixed = static_cast<int16_t *>(outFixed);
+        t.out_float = static_cast<float *>(outFloat);
+        t.inv16 = (h->p.min_disp - 1) * 16;
+        t.invf = (float)(h->p.min_disp - 1);
+        DSX_LAUNCH(h, "texture_mask", st, dsx::launch_texture(t, st));
+    }
     if (h->p.sgbm_post) {
         for (int f = 0; f < nframes; ++f) {
             const size_t fo = (size_t)f * H * W;
@@ -764,6 +869,8 @@ int set_error(int code, const std::string &msg) { return fail(code, msg); }
 }  // namespace dsx
 
 static_assert(dsx::kFillInpaint == DSX_FILL_INPAINT && dsx::kFillNearest == DSX_FILL_NEAREST, "fill methods");
+static_assert(dsx::kPrefNone == DSX_PREFILTER_NONE && dsx::kPrefXsobel == DSX_PREFILTER_XSOBEL &&
+                  dsx::kPrefMean == DSX_PREFILTER_MEAN, "prefilter types");
 static_assert(dsx::kNearestFused == DSX_NEAREST_FUSED && dsx::kNearestStep == DSX_NEAREST_STEPWISE &&
                   dsx::kNearestFusedMaxK == DSX_NEAREST_FUSED_MAX, "nearest paths");
 
@@ -836,10 +943,90 @@ int dsx_set_params(dsx_handle *h, const dsx_params *p) {
     int rc = check(p);  // first: a rejected set reports its own cause, whatever the handle
     if (rc) return rc;
     if (!h) return fail(DSX_EINVAL, "handle is NULL");
+    if (h->pf.type != DSX_PREFILTER_NONE && p->cost == DSX_COST_BT)
+        return fail(DSX_EINVAL, "the handle has a prefilter set (dsx_set_prefilter): cost BT filters for itself; "
+                                "switch the prefilter off first");
     DSX_HIP(hipSetDevice(h->device));
     DSX_HIP(hipStreamSynchronize(h->stream));
     h->p = *p;
     pick_geometry(*p, h->g);
+    return DSX_OK;
+}
+
+void dsx_default_prefilter(dsx_prefilter *f) {
+    if (!f) return;
+    std::memset(f, 0, sizeof(*f));
+    f->type = DSX_PREFILTER_NONE;
+    f->size = 9;
+    f->cap = 31;
+    f->texture_threshold = 0;
+}
+
+int dsx_check_prefilter(const dsx_params *p, const dsx_prefilter *f) {
+    g_err.clear();
+    return check_prefilter(p, f);
+}
+
+int dsx_set_prefilter(dsx_handle *h, const dsx_prefilter *f) {
+    g_err.clear();
+    if (!h) return fail(DSX_EINVAL, "handle is NULL");
+    dsx_prefilter off;
+    dsx_default_prefilter(&off);
+    if (!f) f = &off;
+    int rc = check_prefilter(&h->p, f);
+    if (rc) return rc;
+    DSX_HIP(hipSetDevice(h->device));
+    DSX_HIP(hipStreamSynchronize(h->stream));
+    h->pf = *f;
+    return DSX_OK;
+}
+
+int dsx_prefilter_device(const void *d_img, int32_t H, int32_t W, int64_t stride_bytes, const dsx_prefilter *f,
+                         void *d_out, int64_t out_stride_bytes, void *hip_stream) {
+    g_err.clear();
+    if (!d_img || !d_out) return fail(DSX_EINVAL, "NULL image or output");
+    if (d_img == d_out) return fail(DSX_EINVAL, "d_out must not be d_img (every output reads its neighbours)");
+    int rc = check_prefilter(nullptr, f);
+    if (rc) return rc;
+    if (f->type == DSX_PREFILTER_NONE) return fail(DSX_EINVAL, "prefilter type NONE: nothing to run");
+    if ((rc = check_shape(H, W, stride_bytes))) return rc;
+    if (out_stride_bytes < W) return fail(DSX_EINVAL, "out_stride_bytes must be >= W");
+    dsx::PrefilterArgs a{};
+    a.src[0] = static_cast<const uint8_t *>(d_img);
+    a.stride = stride_bytes;
+    a.dst[0] = static_cast<uint8_t *>(d_out);
+    a.dpitch = out_stride_bytes;
+    a.dwidth = W;  // the caller's rows end at W
+    a.nviews = 1;
+    a.nframes = 1;
+    a.H = H;
+    a.W = W;
+    a.type = f->type;
+    a.n = f->size;
+    a.cap = f->cap;
+    DSX_HIP(dsx::launch_prefilter(a, static_cast<hipStream_t>(hip_stream)));
+    return DSX_OK;
+}
+
+int dsx_texture_sum_device(const void *d_pref, int32_t H, int32_t W, int64_t stride_bytes, int32_t block_size,
+                           int32_t cap, void *d_out_u16, void *hip_stream) {
+    g_err.clear();
+    if (!d_pref || !d_out_u16) return fail(DSX_EINVAL, "NULL image or output");
+    if (block_size < 1 || block_size > 15 || (block_size & 1) == 0)
+        return fail(DSX_EINVAL, "block_size must be odd and in [1, 15]");
+    if (cap < 1 || cap > 63) return fail(DSX_EINVAL, "cap must be in [1, 63]");
+    int rc = check_shape(H, W, stride_bytes);
+    if (rc) return rc;
+    dsx::TextureArgs t{};
+    t.pref = static_cast<const uint8_t *>(d_pref);
+    t.stride = stride_bytes;
+    t.nframes = 1;
+    t.H = H;
+    t.W = W;
+    t.block = block_size;
+    t.cap = cap;
+    t.out_sum = static_cast<uint16_t *>(d_out_u16);
+    DSX_HIP(dsx::launch_texture(t, static_cast<hipStream_t>(hip_stream)));
     return DSX_OK;
 }
 
@@ -1271,7 +1458,9 @@ int dsx_process_pair_device(dsx_handle *h, const void *dL, const void *dR, int32
         const bool fusedp = h->p.path == DSX_PATH_FUSED && !h->p.aggregation && h->p.cost != DSX_COST_BT &&
                             !h->p.sgbm_post;
         const bool lrc = h->p.lr_form == DSX_LR_FORM_SGBM || h->p.disp12_max_diff >= 0;
-        defer = fusedp && lrc && dsx::post_full_two_launch(a) && getenv("DSX_NO_DEFER_LR") == nullptr;
+        // a texture threshold masks the checked map: the fix-up runs in run(), then the mask
+        defer = fusedp && lrc && dsx::post_full_two_launch(a) && h->pf.texture_threshold == 0 &&
+                getenv("DSX_NO_DEFER_LR") == nullptr;
     }
     rc = run(h, dL, dR, H, W, stride_bytes, full ? h->ppFixed : nullptr, full ? nullptr : h->ppDisp, st, 1, 0, defer);
     if (rc) return rc;
@@ -1361,7 +1550,7 @@ int dsx_reset_times(dsx_handle *h) {
 
 int dsx_workspace_bytes(dsx_handle *h, int64_t *bytes) {
     if (!h || !bytes) return fail(DSX_EINVAL, "NULL argument");
-    *bytes = (int64_t)(h->stagingBytes + h->lrKeysBytes + h->dStarBytes + h->vol_bytes + h->btWsBytes +
+    *bytes = (int64_t)(h->stagingBytes + h->pfBytes + h->lrKeysBytes + h->dStarBytes + h->vol_bytes + h->btWsBytes +
                        h->postInBytes + h->postWsBytes + h->sgmSBytes + h->sgmLBytes + h->ppDispBytes +
                        h->ppFixedBytes + h->ppWsBytes);
     return DSX_OK;

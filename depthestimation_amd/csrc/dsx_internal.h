@@ -268,6 +268,35 @@ hipError_t launch_resize_area(const uint8_t *img, int64_t stride, int Hs, int Ws
 bool resize_has_tables();
 void resize_forget_all();  // frees every cached table (dsx_shutdown)
 
+// Matcher prefilter and texture threshold (dsx_prefilter.hip; dsx_prefilter of dsx.h).
+constexpr int kPrefNone = 0, kPrefXsobel = 1, kPrefMean = 2;  // DSX_PREFILTER_*
+struct PrefilterArgs {
+    const uint8_t *src[2];  // view v (nviews of them), frame f at src[v] + f * frame_stride
+    int64_t stride, frame_stride;
+    uint8_t *dst[2];        // view v, frame f at dst[v] + f * dframe, row pitch dpitch
+    int64_t dpitch, dframe;
+    int dwidth;             // writable bytes of an output row (W <= dwidth <= dpitch): rows whose
+                            // start is 16-B aligned are written in 16-B stores up to dwidth
+    int dal;                // set by the launcher: every output row starts 16-B aligned
+    int nviews, nframes, H, W;
+    int type, n, cap;       // kPrefXsobel | kPrefMean (window n, odd, 5..21); cap 1..63
+};
+hipError_t launch_prefilter(const PrefilterArgs &a, hipStream_t st);
+// T = block x block sum of |P - cap| (clamped coordinates) over nframes prefiltered frames.  out_sum
+// (u16, contiguous [nframes][H][W]) set: T is written; otherwise the pixels with T < thr get inv16 in
+// out_fixed and invf in out_float (contiguous [nframes][H][W], either may be null).
+struct TextureArgs {
+    const uint8_t *pref;
+    int64_t stride, frame_stride;
+    int nframes, H, W, block, cap, thr;
+    uint16_t *out_sum;
+    int16_t *out_fixed;
+    float *out_float;
+    int inv16;
+    float invf;
+};
+hipError_t launch_texture(const TextureArgs &a, hipStream_t st);
+
 
 
 }  // namespace dsx

@@ -85,13 +85,20 @@ class HipBlockMatcher:
     def __init__(self, min_disp=0, num_disp=128, block_size=5, cost="sad", uniqueness_ratio=10,
                  disp12_max_diff=1, subpixel=True, float_mode="fixed", path="fused", device=0,
                  timing=False, grid_blocks=0, aggregation=None, p1=0, p2=0, prefilter_cap=31,
-                 sgbm_post=False, speckle_window_size=50, speckle_range=2, lr_form="bm", in_flight=False):
+                 sgbm_post=False, speckle_window_size=50, speckle_range=2, lr_form="bm", in_flight=False,
+                 prefilter_type="none", prefilter_size=9, texture_threshold=0):
+        """``prefilter_type`` 'xsobel' | 'mean' filters both views on the device before the search
+        (``prefilter_cap`` is its cap, ``prefilter_size`` the window of 'mean'); ``texture_threshold`` > 0
+        then invalidates the pixels whose filtered block has less texture (depthestimation_amd/prefilter.py
+        restates both).  The defaults ('none', 0) run no extra kernel."""
         self.device = int(device)
         self._params = _dsx.make_params(min_disp, num_disp, block_size, cost, uniqueness_ratio,
                                         disp12_max_diff, subpixel, float_mode, path, timing,
                                         grid_blocks, aggregation, p1, p2, prefilter_cap, sgbm_post,
                                         speckle_window_size, speckle_range, lr_form, in_flight)
         _dsx.check_params(self._params)  # validates on the host, no device needed
+        self._prefilter = _dsx.make_prefilter(prefilter_type, prefilter_size, prefilter_cap, texture_threshold)
+        _dsx.check_prefilter(self._params, self._prefilter)
         self._h = None
         self._cfg = dict(min_disp=min_disp, num_disp=num_disp, block_size=block_size, cost=cost,
                          uniqueness_ratio=uniqueness_ratio, disp12_max_diff=disp12_max_diff,
@@ -99,7 +106,20 @@ class HipBlockMatcher:
                          grid_blocks=grid_blocks, aggregation=aggregation, p1=p1, p2=p2,
                          prefilter_cap=prefilter_cap, sgbm_post=sgbm_post,
                          speckle_window_size=speckle_window_size, speckle_range=speckle_range, lr_form=lr_form,
-                         in_flight=in_flight)
+                         in_flight=in_flight, prefilter_type=prefilter_type, prefilter_size=prefilter_size,
+                         texture_threshold=texture_threshold)
+
+    _PREFILTER_DEFAULTS = {"prefilter_type": "none", "prefilter_size": 9, "texture_threshold": 0}
+    _PREFILTER_KEYS = tuple(_PREFILTER_DEFAULTS)
+
+    @classmethod
+    def _split_cfg(cls, cfg):
+        """(dsx_params, dsx_prefilter) of a configuration dict."""
+        base = {k: v for k, v in cfg.items() if k not in cls._PREFILTER_KEYS}
+        params = _dsx.make_params(**base)
+        pre = _dsx.make_prefilter(cfg["prefilter_type"], cfg["prefilter_size"], cfg["prefilter_cap"],
+                                  cfg["texture_threshold"])
+        return params, pre
 
     # -- lifetime ---------------------------------------------------------------------------
     def _handle(self):
@@ -110,6 +130,11 @@ class HipBlockMatcher:
                 raise RuntimeError("HipBlockMatcher: no HIP device visible (the engine has no CPU fallback)")
             h = ctypes.c_void_p()
             _dsx.check(L.dsx_create(self.device, ctypes.byref(self._params), ctypes.byref(h)), "dsx_create")
+            if self._prefilter.type != _dsx.PREFILTER["none"]:
+                rc = L.dsx_set_prefilter(h, ctypes.byref(self._prefilter))
+                if rc != _dsx.DSX_OK:
+                    L.dsx_destroy(h)
+                    _dsx.check(rc, "dsx_set_prefilter")
             self._h = h
         return self._h
 
@@ -126,7 +151,19 @@ class HipBlockMatcher:
 
     @property
     def params(self) -> dict:
-        return dict(self._cfg)
+        """The constructor keywords of this matcher.  The prefilter keys are reported once any of them
+        is off its default ('none', 9, 0), so a matcher without a prefilter reports the set it always
+        did; ``prefilter_params`` reports them always."""
+        cfg = dict(self._cfg)
+        if all(cfg[k] == d for k, d in self._PREFILTER_DEFAULTS.items()):
+            for k in self._PREFILTER_DEFAULTS:
+                del cfg[k]
+        return cfg
+
+    @property
+    def prefilter_params(self) -> dict:
+        """{'prefilter_type', 'prefilter_size', 'prefilter_cap', 'texture_threshold'} in effect."""
+        return {k: self._cfg[k] for k in ("prefilter_type", "prefilter_size", "prefilter_cap", "texture_threshold")}
 
     def set_params(self, **kw):
         """Replace parameters of this matcher (dsx_set_params; configure_sgbm -> _build_sgbm,
@@ -139,15 +176,30 @@ class HipBlockMatcher:
             raise ValueError(f"set_params: unknown parameter(s) {unknown}; known: {sorted(self._cfg)}")
         cfg = dict(self._cfg, **kw)
         try:
-            params = _dsx.make_params(**cfg)
+            params, pre = self._split_cfg(cfg)
         except (TypeError, OverflowError) as e:
             raise ValueError(f"set_params: {e}") from e
         _dsx.check_params(params)
+        _dsx.check_prefilter(params, pre)
         if self._h is not None:
-            rc = _dsx.lib().dsx_set_params(self._h, ctypes.byref(params))
-            if rc != _dsx.DSX_OK:
-                raise ValueError(f"dsx_set_params: {_dsx.last_error() or 'error ' + str(rc)}")
-        self._params, self._cfg = params, cfg
+            L = _dsx.lib()
+
+            def set_p():
+                rc = L.dsx_set_params(self._h, ctypes.byref(params))
+                if rc != _dsx.DSX_OK:
+                    raise ValueError(f"dsx_set_params: {_dsx.last_error() or 'error ' + str(rc)}")
+
+            def set_f():
+                rc = L.dsx_set_prefilter(self._h, ctypes.byref(pre))
+                if rc != _dsx.DSX_OK:
+                    raise ValueError(f"dsx_set_prefilter: {_dsx.last_error() or 'error ' + str(rc)}")
+
+            # each setter validates against the other's current value, and the pair was validated
+            # together above: a filter that goes off leaves first (the new cost may be 'bt'), one that
+            # comes on or changes arrives after the parameters it was checked with
+            for step in ((set_f, set_p) if pre.type == _dsx.PREFILTER["none"] else (set_p, set_f)):
+                step()
+        self._params, self._prefilter, self._cfg = params, pre, cfg
 
     # -- cv2.StereoMatcher-style getters (cv2 names used by depthlib docs) --------------------
     def getMinDisparity(self):
@@ -366,6 +418,48 @@ def postprocess_fast_device(disp, crop, focal_length=None, baseline=None, doffs=
         float(doffs or 0.0), float(eps), float(max_depth or 0.0), int(max_depth is not None), sptr)
     _dsx.check(rc, "dsx_postprocess_fast_device")
     return out_disp, (out_depth if want_depth else None)
+
+
+def prefilter_device(img, prefilter_type="xsobel", prefilter_size=9, prefilter_cap=31, out=None, stream=None):
+    """The matcher prefilter alone on the device (dsx_prefilter_device; host restatement
+    depthestimation_amd/prefilter.py): ``img`` uint8 H x W HIP tensor (unit column stride, any row stride
+    or offset) -> uint8 H x W in [0, 2 * prefilter_cap]."""
+    import torch
+
+    if img.dtype != torch.uint8 or img.dim() != 2 or not img.is_cuda or img.stride(1) != 1:
+        raise ValueError("img must be a uint8 H x W device tensor with unit column stride")
+    f = _dsx.make_prefilter(prefilter_type, prefilter_size, prefilter_cap, 0)
+    H, W = img.shape
+    if out is None:
+        out = torch.empty((H, W), dtype=torch.uint8, device=img.device)
+    elif out.dtype != torch.uint8 or out.shape != (H, W) or out.stride(1) != 1 or out.device != img.device:
+        raise ValueError("out must be a uint8 H x W tensor with unit column stride on the input's device")
+    if H == 0 or W == 0:
+        return out
+    rc = _dsx.lib().dsx_prefilter_device(img.data_ptr(), H, W, img.stride(0), ctypes.byref(f), out.data_ptr(),
+                                         out.stride(0), _stream_ptr(stream))
+    _dsx.check(rc, "dsx_prefilter_device")
+    return out
+
+
+def texture_sum_device(pref, block_size, cap=31, stream=None):
+    """T of a prefiltered image on the device (dsx_texture_sum_device): the block_size x block_size sum
+    of |P - cap| with clamped coordinates, int32 H x W HIP tensor (the kernel's uint16 values)."""
+    import torch
+
+    if pref.dtype != torch.uint8 or pref.dim() != 2 or not pref.is_cuda or pref.stride(1) != 1:
+        raise ValueError("pref must be a uint8 H x W device tensor with unit column stride")
+    H, W = pref.shape
+    out = torch.empty((H, W), dtype=torch.int16, device=pref.device)
+    if H and W:
+        rc = _dsx.lib().dsx_texture_sum_device(pref.data_ptr(), H, W, pref.stride(0), int(block_size), int(cap),
+                                               out.data_ptr(), _stream_ptr(stream))
+        _dsx.check(rc, "dsx_texture_sum_device")
+    if stream is None:
+        return out.to(torch.int32) & 0xFFFF
+    st = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(stream), device=pref.device)
+    with torch.cuda.stream(st):  # the widening follows the kernel on its stream
+        return out.to(torch.int32) & 0xFFFF
 
 
 def rectify_device(img, mapx=None, mapy=None, out=None, stream=None):

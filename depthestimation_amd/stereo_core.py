@@ -29,8 +29,15 @@ Keys added to ``sgbm_params`` (accepted by ``configure_sgbm`` like the reference
                                        'inpaint', the default and the reference's choice, is Telea's
                                        march; 'nearest' is the iterated dilation - bounded, stateless,
                                        nothing to time out, and fast enough for video)
+  'prefilter_type': 'none' | 'xsobel' | 'mean'  ('none', the default: raw intensities.  cv2.StereoBM's
+                                       prefilter in this build's arithmetic (prefilter.py): both views are
+                                       filtered on the device before the SAD / SSD search, which makes it
+                                       usable on cameras of unequal exposure or shading; 'prefilter_cap' is
+                                       the cap, 'prefilter_size' (odd, 5..21) the window of 'mean')
+  'texture_threshold': int            (0 = off; > 0 needs a prefilter: pixels whose filtered block sums
+                                       less than this much |P - cap| become invalid)
 Keys of the reference that have no block-matching meaning are kept, validated and reported
-but do not change the result: 'prefilter_cap' unless 'cost' is 'bt', 'speckle_window_size' /
+but do not change the result: 'prefilter_cap' unless 'cost' is 'bt' or a prefilter is set, 'speckle_window_size' /
 'speckle_range' unless 'sgbm_post' is set, and 'sgbm_mode' / P1 / P2 while 'aggregation' is 'none'
 (SURVEY.md 8a A5').  cost='bt' + aggregation='sgm' + lr_form='sgbm' + sgbm_post=True is this build's
 closest form of the reference's cv2.StereoSGBM.
@@ -126,6 +133,9 @@ class StereoCore:
             'sgbm_post': False,
             'lr_form': 'bm',
             'fill_method': 'inpaint',
+            'prefilter_type': 'none',
+            'prefilter_size': 9,
+            'texture_threshold': 0,
         }
         self._build_sgbm()
         self.disparity_map = None
@@ -161,6 +171,9 @@ class StereoCore:
             speckle_window_size=p['speckle_window_size'],
             speckle_range=p['speckle_range'],
             lr_form=p.get('lr_form', 'bm'),
+            prefilter_type=p.get('prefilter_type', 'none'),
+            prefilter_size=p.get('prefilter_size', 9),
+            texture_threshold=p.get('texture_threshold', 0),
         )
         if old is not None:
             old.close()

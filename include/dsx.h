@@ -34,6 +34,8 @@ extern "C" {
 
 #define DSX_VERSION 106 /* additive since 1.0.6 (layouts unchanged): dsx_resize_area_*, dsx_fill_nearest_*,
                            dsx_postprocess_device,
+                           dsx_prefilter, dsx_default_prefilter, dsx_check_prefilter, dsx_set_prefilter,
+                           dsx_prefilter_device, dsx_texture_sum_device (matcher prefilter + texture threshold);
                            dsx_post_params.fill_method (a former reserved slot; 0 = as before);
                            1.0.6: hole filling in OpenCV's own arithmetic and exact queue order, dsx_fill_holes_release,
                            dsx_shutdown;
@@ -136,9 +138,57 @@ int dsx_create(int device, const dsx_params *p, dsx_handle **out);
 
 /* Replace the parameters of an existing matcher (configure_sgbm -> _build_sgbm,
  * stereo_core.py:77-123). The parameters are validated first (DSX_EINVAL names the cause and the
- * handle keeps its old set). The next call grows every cached device buffer that the new set needs
- * larger (e.g. the SGM buffer with the direction count); a buffer may stay larger than needed. */
+ * handle keeps its old set; so does a switch to DSX_COST_BT while a prefilter is set). The next
+ * call grows every cached device buffer that the new set needs larger (e.g. the SGM buffer with the
+ * direction count); a buffer may stay larger than needed. */
 int dsx_set_params(dsx_handle *h, const dsx_params *p);
+
+/* Matcher prefilter and texture threshold (cv2.StereoBM's preFilterType / preFilterSize / preFilterCap /
+ * textureThreshold, in this build's own arithmetic; parity with OpenCV unpinned).  With c = cap, cx / cy the
+ * replicate clamp into the image:
+ *   DSX_PREFILTER_XSOBEL: P(x, y) = clip(Sx, -c, c) + c,
+ *       Sx = 2 (I(x+1, y) - I(x-1, y)) + I(x+1, cy(y-1)) - I(x-1, cy(y-1)) + I(x+1, cy(y+1)) - I(x-1, cy(y+1));
+ *       columns 0 and W-1 hold c.
+ *   DSX_PREFILTER_MEAN (window n = size): S = sum of I(cx(x+i), cy(y+j)) over |i|, |j| <= n/2,
+ *       mu = (S + n*n/2) / (n*n) (integer division), P = clip(I - mu, -c, c) + c.
+ * P is uint8 in [0, 2c].  Both views are filtered into handle-owned buffers and the matcher runs on them
+ * exactly as it runs on raw images (any SAD / SSD configuration; dsx_right_map_device too).
+ *   texture_threshold t > 0 (needs a prefilter): T(x, y) = sum of |P_L(cx(x+i), cy(y+j)) - c| over the
+ *       matcher's block window; a pixel with T < t gets the invalid value ((min_disp - 1) * 16; min_disp - 1
+ *       in the float map) after uniqueness, sub-pixel and the LR check, before the sgbm_post tail.
+ * DSX_COST_BT filters for itself: BT with a prefilter is DSX_EINVAL.  With type NONE and threshold 0
+ * (the default) a handle runs no extra launch and owns no extra buffer. */
+#define DSX_PREFILTER_NONE 0
+#define DSX_PREFILTER_XSOBEL 1
+#define DSX_PREFILTER_MEAN 2
+typedef struct dsx_prefilter {
+    int32_t type;              /* DSX_PREFILTER_*                                                   */
+    int32_t size;              /* window of DSX_PREFILTER_MEAN: odd, 5..21 (checked for any filter)  */
+    int32_t cap;               /* 1..63                                                             */
+    int32_t texture_threshold; /* 0 (off) .. 65535                                                  */
+    int32_t reserved[4];
+} dsx_prefilter;
+
+/* none, size 9, cap 31, threshold 0 */
+void dsx_default_prefilter(dsx_prefilter *f);
+
+/* Validate a prefilter, alone (p NULL) or against matcher parameters (no handle, no device). */
+int dsx_check_prefilter(const dsx_params *p, const dsx_prefilter *f);
+
+/* Set the handle's prefilter (NULL = off), validated against its current parameters; on error the
+ * handle keeps its old set.  dsx_set_params in turn validates new parameters against the prefilter. */
+int dsx_set_prefilter(dsx_handle *h, const dsx_prefilter *f);
+
+/* The filter alone, for callers that filter themselves (stateless, asynchronous on hip_stream):
+ * d_img uint8 H x W with row stride stride_bytes -> d_out uint8 H x W with row stride out_stride_bytes
+ * (not d_img).  Any alignment; 16-B aligned rows take the wide loads / stores. */
+int dsx_prefilter_device(const void *d_img, int32_t H, int32_t W, int64_t stride_bytes, const dsx_prefilter *f,
+                         void *d_out, int64_t out_stride_bytes, void *hip_stream);
+
+/* T of a prefiltered image: d_out_u16 contiguous uint16 H x W (at most 225 * 63 for a filtered image).
+ * block_size odd, 1..15; cap 1..63.  Stateless, asynchronous on hip_stream. */
+int dsx_texture_sum_device(const void *d_pref, int32_t H, int32_t W, int64_t stride_bytes, int32_t block_size,
+                           int32_t cap, void *d_out_u16, void *hip_stream);
 
 /* Synchronous host-buffer compute (replaces matcher.compute, stereo_core.py:231).
  * L, R: uint8 H x W with row stride `stride_bytes` (>= W).  out_fixed: int16 H x W
@@ -151,10 +201,10 @@ int dsx_compute_host(dsx_handle *h, const uint8_t *L, const uint8_t *R, int32_t 
  * d_out_float (float32) are contiguous H x W device buffers; either may be NULL but not
  * both.  No host synchronisation, no allocation when the size matches the cached one.
  * Calls on different streams through ONE handle are safe: a configuration that uses the handle's
- * scratch (LR check, volume path, BT cost, SGM, sgbm_post) orders a call on a new stream after the
- * previous call's last kernel (stream wait on an event, no host wait); the plain fused pass owns no
- * scratch and runs concurrently.  Inputs and outputs are the caller's: they must stay valid and
- * unmodified until the work on hip_stream has completed. */
+ * scratch (LR check, volume path, BT cost, SGM, sgbm_post, a prefilter's filtered images) orders a call
+ * on a new stream after the previous call's last kernel (stream wait on an event, no host wait); the
+ * plain fused pass without a prefilter owns no scratch and runs concurrently.  Inputs and outputs
+ * are the caller's: they must stay valid and unmodified until the work on hip_stream has completed. */
 int dsx_compute_device(dsx_handle *h, const void *dL, const void *dR, int32_t H, int32_t W,
                        int64_t stride_bytes, void *d_out_fixed, void *d_out_float,
                        void *hip_stream);
@@ -380,8 +430,8 @@ int dsx_kernel_times(dsx_handle *h, char *names, int names_cap, float *ms, int *
 int dsx_reset_times(dsx_handle *h);
 
 /* Device bytes currently held by the handle's buffer cache: the host-call staging images and
- * outputs, the LR keys and left winners, the cost volume, the BT records, the SGM sums of either
- * form, the sgbm_post input and workspace, and dsx_process_pair_device's maps and workspace.
+ * outputs, the prefiltered images, the LR keys and left winners, the cost volume, the BT records,
+ * the SGM sums of either form, the sgbm_post input and workspace, and dsx_process_pair_device's maps and workspace.
  * Buffers kept from an earlier parameter set count until a shape or geometry change frees them. */
 int dsx_workspace_bytes(dsx_handle *h, int64_t *bytes);
 

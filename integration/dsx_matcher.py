@@ -19,6 +19,15 @@ class _Params(ctypes.Structure):
         "prefilter_cap", "sgbm_post", "speckle_window_size", "speckle_range", "lr_form", "in_flight")] + [("reserved", ctypes.c_int32 * 2)]
 
 
+class _Prefilter(ctypes.Structure):
+    # dsx_prefilter (include/dsx.h)
+    _fields_ = [(n, ctypes.c_int32) for n in ("type", "size", "cap", "texture_threshold")] + [
+        ("reserved", ctypes.c_int32 * 4)]
+
+
+# preFilterType names -> DSX_PREFILTER_* (this build's own arithmetic, see include/dsx.h)
+PREFILTERS = {None: 0, "none": 0, "xsobel": 1, "mean": 2}
+
 # sgbm_mode names (stereo_core.py:55-61) -> DSX_AGG_* (semi-global aggregation over SAD costs)
 SGBM_MODES = {"sgbm_3way": 3, "hh4": 4, "sgbm": 5, "hh": 8}
 
@@ -31,6 +40,7 @@ _lib.dsx_create.argtypes = [ctypes.c_int, _P, ctypes.POINTER(_vp)]
 _lib.dsx_compute_host.argtypes = [_vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _vp, _vp]
 _lib.dsx_destroy.argtypes = [_vp]
 _lib.dsx_last_error.restype = ctypes.c_char_p
+_lib.dsx_set_prefilter.argtypes = [_vp, ctypes.POINTER(_Prefilter)]
 
 
 def make_params(minDisparity=0, numDisparities=128, blockSize=5, disp12MaxDiff=1, uniquenessRatio=10,
@@ -54,13 +64,22 @@ class DsxStereoMatcher:
 
     def __init__(self, minDisparity=0, numDisparities=128, blockSize=5, disp12MaxDiff=1,
                  uniquenessRatio=10, cost=0, device=0, sgbm_mode=None, P1=0, P2=0, preFilterCap=31,
-                 **_sgbm_only_keys):
+                 preFilterType=None, preFilterSize=9, textureThreshold=0, **_sgbm_only_keys):
+        # preFilterType 'xsobel' | 'mean' (cv2.StereoBM's keyword names): both views are filtered on the
+        # device before the SAD / SSD search, cap preFilterCap; textureThreshold > 0 needs one
         p = make_params(minDisparity, numDisparities, blockSize, disp12MaxDiff, uniquenessRatio, cost,
                         sgbm_mode, P1, P2, preFilterCap)
         self._h = _vp()
         if _lib.dsx_create(device, ctypes.byref(p), ctypes.byref(self._h)) != 0:
             self._h = None
             raise RuntimeError(_lib.dsx_last_error().decode())
+        if PREFILTERS[preFilterType] or textureThreshold:
+            f = _Prefilter(PREFILTERS[preFilterType], preFilterSize, preFilterCap, textureThreshold)
+            if _lib.dsx_set_prefilter(self._h, ctypes.byref(f)) != 0:
+                msg = _lib.dsx_last_error().decode()
+                _lib.dsx_destroy(self._h)
+                self._h = None
+                raise ValueError(msg)
 
     def compute(self, left, right):
         L = np.ascontiguousarray(left, np.uint8)
