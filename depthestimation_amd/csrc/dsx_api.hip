@@ -484,6 +484,7 @@ dsx::Bm2Args base_args(dsx_handle *h, int H, int W, int64_t stride, const DsxEnv
         // in_flight handles: no priority bands and equal age weights (profiles/r04af_balance_in_flight.txt:
         // C4 19.5k -> 20.8k Mpix/s with 3 frames in flight; a lone launch needs the balance)
         const bool fl = h->p.in_flight != 0;
+        a.in_flight = fl ? 1 : 0;
         a.prio = env.prio ? atoi(env.prio) : (fl ? 0 : 1);
         a.pt1 = 128, a.pt2 = 205, a.pt3 = 243;
         if (env.prio_t) sscanf(env.prio_t, "%d,%d,%d", &a.pt1, &a.pt2, &a.pt3);

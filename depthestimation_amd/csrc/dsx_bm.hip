@@ -62,6 +62,20 @@ constexpr int kWpeSsd = 4;  // SSD blocks of >= 4 waves
 #ifndef DSX_ROWSTEP_AHEAD
 #define DSX_ROWSTEP_AHEAD 1
 #endif
+// -DDSX_ROWSTEP_SREF=1 switches ON the reference row of the rotated loop's unaligned-dword copy through the scalar
+// unit (SREF in bm2_segment) instead of broadcast LDS reads, which is off by default: the C2 loop then holds 20
+// ds_read_b128 and 4 VALU fewer per step, spills nothing, and ran 10 % slower (one-stream kernel 51.3 -> 56.7 us,
+// 44.8k -> 41.2k Mpix/s with three frames in flight; DESIGN 4.4, profiles/sref_ab.txt).  -DDSX_ROWSTEP_SARGS
+// (default: as SREF) is its second half on its own switch: the stages behind the last chunk re-read their launch
+// arguments, which frees the SGPRs the dwords need; alone it costs 0.3 us.
+#ifndef DSX_ROWSTEP_SREF
+#define DSX_ROWSTEP_SREF 0
+#endif
+#ifndef DSX_ROWSTEP_SARGS
+#define DSX_ROWSTEP_SARGS DSX_ROWSTEP_SREF
+#endif
+constexpr bool kRowstepSref = DSX_ROWSTEP_SREF;          // pair layout, one-wave left pass, R <= 4
+constexpr bool kRowstepSargs = DSX_ROWSTEP_SARGS;        // the same loops: launch arguments re-read behind the last chunk
 constexpr bool kRowstepOverlap = DSX_ROWSTEP_OVERLAP;    // pair layout, one-wave left pass, R <= 5
 constexpr bool kRowstepAhead = DSX_ROWSTEP_AHEAD;        // pair layout, one-wave left pass, R <= 5
 constexpr bool kRowstepPairtail = DSX_ROWSTEP_PAIRTAIL;  // pair layout, one-wave left pass
@@ -754,6 +768,36 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
     constexpr bool CUQ = !SSD && SIDE == 0 && NW == 1 && R < 6 && kRowstepKey2 && !PTAIL;
     constexpr bool OVL = kRowstepOverlap && CUQ, AHD = kRowstepAhead && CUQ;
     constexpr int CQ = 4, NQ = (NC + CQ - 1) / CQ;
+    // SREF (the unaligned-dword copy of these loops): the reference row is wave-uniform, so the column update takes
+    // it from SGPRs - v_sad_u8 / v_sad_hi_u8 are VOP3 and read the reference byte as their one scalar operand -
+    // instead of 2 * NC4 broadcast ds_read_b128 per step.  A row is bytes [x0 - R, x0 - R + 4 NC4) of the reference
+    // image, inside the row by the segment's FAST test; the pointer has any alignment, so a step reads the aligned
+    // dwords that hold one of those bytes (NC4, + 1 when misaligned: the last offset below repeats dword NC4 - 1 when
+    // aligned, never a dword past the row's last needed byte), and chunk q takes its dword with one s_lshr_b64 of
+    // dwords q, q + 1 and each column's byte with one s_and / s_bfe / s_lshr.  Scalar memory returns out of order
+    // with LDS operations, so its consumer waits with lgkmcnt(0): the two rows of step y + 1 are loaded in one batch
+    // behind step y's last chunk, where step y's dwords are dead, and first used by chunk 0 of step y + 1, the one
+    // chunk that waits for its LDS reads anyway.  Read only; the clamped copy and the init keep the LDS form.
+    // R = 5 (12 dwords per row) keeps the LDS form: with SREF its kernel spills 8 B to scratch at the segment starts.
+    constexpr bool SREF = kRowstepSref && CUQ && FAST && OVL && R < 5;
+    // SRA: both copies of such a loop re-read the launch arguments of the stages behind the chunks (ea in estage)
+    constexpr bool SRA = kRowstepSargs && CUQ && OVL && R < 5;
+    static_assert(!SREF || NQ == NC4, "one reference dword per column chunk");
+    uint32_t qn[NC4 + 1] = {}, qo[NC4 + 1] = {}, shn = 0, sho = 0;
+    auto sld = [&](int r, uint32_t(&q)[NC4 + 1], uint32_t &sh) __attribute__((always_inline)) {
+        const int yy = clampi2(r, 0, H - 1);
+        const uintptr_t p = (uintptr_t)(a.ref + fin + (long)yy * stride + (x0 - R));
+        typedef const __attribute__((address_space(4))) uint8_t cu8;
+        cu8 *b = (cu8 *)(p & ~(uintptr_t)3);
+#pragma unroll
+        for (int i = 0; i < NC4; ++i) q[i] = *(cu32 *)(b + 4 * i);
+        q[NC4] = *(cu32 *)(b + ((((uint32_t)p + 4u * NC4 - 1u) & ~3u) - ((uint32_t)p & ~3u)));
+        sh = ((uint32_t)p & 3u) * 8u;
+    };
+    // column c0 + c's reference byte of a row's dword (its misalignment shifted out)
+    auto sbyte = [](uint32_t w, int c) __attribute__((always_inline)) -> uint32_t {
+        return c == 3 ? w >> 24 : (w >> (8 * c)) & 0xFFu;
+    };
     // Tile reads per stage and read stages: one read (4 VGPRs in flight) where the chunks suffice, two otherwise.
     // With two, R = 4 and R = 5 spilled 8 B with both forms on; four overran the 168 VGPRs with OVL alone.
     // Stages 0 .. NRS - 1 read, NRS block keys, NRS + 1 element keys, NRS + 2 sub-pixel step, NRS + 3 outputs.
@@ -770,8 +814,16 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
                                                    __builtin_elementwise_min(as2(v.z), as2(v.w)));
         return umin2(mm.x, mm.y);
     };
-    auto estage = [&](auto sc, int ey) __attribute__((always_inline)) {
+    // rl / er: the sub-pixel and output stages read their launch arguments from er (SRA: the row loop's re-read ones
+    // behind its last chunk) instead of the segment's
+    auto estage = [&](auto sc, int ey, auto rl, const Bm2Args &er) __attribute__((always_inline)) {
         constexpr int s = decltype(sc)::value;
+        constexpr bool RL = decltype(rl)::value;
+        auto pick = [&]() __attribute__((always_inline)) -> const Bm2Args & {
+            if constexpr (RL) return er;
+            else return a;
+        };
+        const Bm2Args &ea = pick();
         static_assert(!OVL || (NB == 8 && TPP == 2), "overlapped epilogue: 64 disparities per lane, two lanes per pixel");
         constexpr int GB = Dp / 8 <= 16 ? 4 : (Dp / 8 <= 32 ? 5 : 6);
         if constexpr (s <= NRS) {  // RPS block reads per stage; the block keys (KEY2 of the sequential form) of those before
@@ -802,15 +854,16 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
             ecm = pc[-1];
             ecp = pc[1];
         } else if constexpr (s == NRS + 2) {  // sub-pixel step
-            esp = a.subpix && eb > 0 && eb < D - 1;
+            esp = ea.subpix && eb > 0 && eb < D - 1;
             int32_t den = (int32_t)ecm + (int32_t)ecp - 2 * (int32_t)ecb;
             eden = den < 1 ? 1 : den;
             const int32_t num = ((int32_t)ecm - (int32_t)ecp) * 16 + eden;
             const int32_t q = DIVQ ? subpix_quot(num, 2 * eden) : div_trunc_small(num, 2 * eden);
             ef = eb * 16 + (esp ? q : 0);
         } else {  // uniqueness, outputs
+            const uint32_t padv_e = RL ? er.padv : padv;
             bool valid = ex < W && ex >= m + D - 1 && ex <= W - 1 + m;
-            if (a.uniq > 0) {
+            if (ea.uniq > 0) {
                 const int rel = eb - eh * DSL;
                 uint32_t nm = 0xFFFFFFFFu;
 #pragma unroll
@@ -835,25 +888,29 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
                     }
                 }
                 nm = gmin<TPP>(nm);
-                const uint32_t real_max = padv < (1u << 24) ? padv : (1u << 24);
-                if (nm < real_max && nm * (uint32_t)(100 - a.uniq) < ecb * 100u) valid = false;
+                const uint32_t real_max = padv_e < (1u << 24) ? padv_e : (1u << 24);
+                if (nm < real_max && nm * (uint32_t)(100 - ea.uniq) < ecb * 100u) valid = false;
             }
             if (eh == 0 && ex < W) {
                 const long o = fout + (long)ey * W + ex;
                 const int16_t fx = valid ? (int16_t)(m * 16 + ef) : (int16_t)((m - 1) * 16);
-                if (a.out_fixed) a.out_fixed[o] = fx;
-                if (a.out_float) {
-                    if (a.float_mode == 0) {
-                        a.out_float[o] = (float)fx * 0.0625f;
+                if (ea.out_fixed) ea.out_fixed[o] = fx;
+                if (ea.out_float) {
+                    if (ea.float_mode == 0) {
+                        ea.out_float[o] = (float)fx * 0.0625f;
                     } else {
                         float pf = (float)(m + eb);
                         if (esp) pf = (float)(m + eb) + (float)((int32_t)ecm - (int32_t)ecp) / (float)(2 * eden);
-                        a.out_float[o] = valid ? pf : (float)(m - 1);
+                        ea.out_float[o] = valid ? pf : (float)(m - 1);
                     }
                 }
             }
         }
     };
+    if constexpr (SREF) {  // the rows of the segment's first column update (step yb + 1)
+        sld(yb + 1 + R, qn, shn);
+        sld(yb - R, qo, sho);
+    }
     for (int y = yb; y < ye; ++y) {
         const Bm2Args &a = kargs_row<SIDE == 3>(a_in);
 #ifdef DSX_STAMPS
@@ -932,10 +989,12 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
                 constexpr int q = decltype(qc)::value, c0 = CQ * q, t = AHD ? (q & 1) : 0;
                 const uint8_t *bn = (const uint8_t *)__builtin_assume_aligned(smem + par * SLOT + d0 * 4, 8);
                 const uint8_t *bo = (const uint8_t *)__builtin_assume_aligned(smem + (par + 1) * SLOT + d0 * 4, 8);
-                const uint4 vn = *reinterpret_cast<const uint4 *>(smem + par * SLOT + G::SROW + 4 * c0);
-                const uint4 vo = *reinterpret_cast<const uint4 *>(smem + (par + 1) * SLOT + G::SROW + 4 * c0);
-                rn[t][0] = vn.x; rn[t][1] = vn.y; rn[t][2] = vn.z; rn[t][3] = vn.w;
-                ro[t][0] = vo.x; ro[t][1] = vo.y; ro[t][2] = vo.z; ro[t][3] = vo.w;
+                if constexpr (!SREF) {
+                    const uint4 vn = *reinterpret_cast<const uint4 *>(smem + par * SLOT + G::SROW + 4 * c0);
+                    const uint4 vo = *reinterpret_cast<const uint4 *>(smem + (par + 1) * SLOT + G::SROW + 4 * c0);
+                    rn[t][0] = vn.x; rn[t][1] = vn.y; rn[t][2] = vn.z; rn[t][3] = vn.w;
+                    ro[t][0] = vo.x; ro[t][1] = vo.y; ro[t][2] = vo.z; ro[t][3] = vo.w;
+                }
                 sn[t][0] = c0 == 0 ? *reinterpret_cast<const uint32_t *>(bn + NC * 4) : nxn;
                 so[t][0] = c0 == 0 ? *reinterpret_cast<const uint32_t *>(bo + NC * 4) : nxo;
 #pragma unroll
@@ -950,11 +1009,23 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
             };
             auto sads = [&](auto qc) __attribute__((always_inline)) {
                 constexpr int q = decltype(qc)::value, c0 = CQ * q, t = AHD ? (q & 1) : 0;
+                // SREF: the chunk's reference dword of either row, on the scalar unit
+                uint32_t wn = 0, wo = 0;
+                if constexpr (SREF) {
+                    // the upper dword passes through an empty asm (in place, no instruction): left free, the two
+                    // array elements are combined into one 64-bit access, which keeps the arrays out of registers
+                    uint32_t hn = qn[q + 1], ho = qo[q + 1];
+                    asm("" : "+s"(hn));
+                    asm("" : "+s"(ho));
+                    wn = (uint32_t)((((uint64_t)hn << 32) | qn[q]) >> shn);
+                    wo = (uint32_t)((((uint64_t)ho << 32) | qo[q]) >> sho);
+                }
 #pragma unroll
                 for (int c = 0; c < CQ; ++c) {
                     if (c0 + c < NC) {
-                        const uint32_t en = sad_hi_u8(rn[t][c], sn[t][c], __builtin_amdgcn_sad_u8(rn[t][c], sn[t][c + 1], as1(cs[c0 + c])));
-                        const uint32_t lo = sad_hi_u8(ro[t][c], so[t][c], __builtin_amdgcn_sad_u8(ro[t][c], so[t][c + 1], 0u));
+                        const uint32_t bn = SREF ? sbyte(wn, c) : rn[t][c], bo = SREF ? sbyte(wo, c) : ro[t][c];
+                        const uint32_t en = sad_hi_u8(bn, sn[t][c], __builtin_amdgcn_sad_u8(bn, sn[t][c + 1], as1(cs[c0 + c])));
+                        const uint32_t lo = sad_hi_u8(bo, so[t][c], __builtin_amdgcn_sad_u8(bo, so[t][c + 1], 0u));
                         // pinned to this chunk (in place, no instruction): left free, the SADs - pure values whose
                         // next use is the box phase - are sunk behind the epilogue's branches, every staged
                         // word of the step is then held across it, and the loop spills
@@ -969,7 +1040,7 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
                 constexpr int q = decltype(qc)::value;
                 if constexpr (q < NQ) {
                     __builtin_amdgcn_sched_barrier(0);
-                    if constexpr (OVL && q < NRS + 3) estage(qc, y - 1);
+                    if constexpr (OVL && q < NRS + 3) estage(qc, y - 1, std::false_type{}, a);
                     if constexpr (!AHD) rd(qc);
                     else if constexpr (q + 1 < NQ) rd(std::integral_constant<int, q + 1>{});
                     __builtin_amdgcn_sched_barrier(0);
@@ -985,9 +1056,17 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
             chunk(std::integral_constant<int, 10>{}); chunk(std::integral_constant<int, 11>{});
             static_assert(NQ <= 12 && NQ >= 7, "chunks of the overlapped column update");
             __builtin_amdgcn_sched_barrier(0);
+            if constexpr (SREF) {  // step y + 1's rows (clamped like the prefetch: the segment's last step reads a row nobody uses)
+                sld(y + 1 + R, qn, shn);
+                sld(y - R, qo, sho);
+            }
+            // SREF: the stages behind the chunks re-read their launch arguments in the same batch (kargs_row), like the
+            // LR pass's row loop: held across the loop next to the reference dwords they spill to VGPR lanes
+            const Bm2Args &ea = kargs_row<SRA>(a);
+            if constexpr (SRA) __builtin_amdgcn_sched_barrier(0);
             if constexpr (OVL) {
-                if constexpr (NQ < NRS + 3) estage(std::integral_constant<int, NRS + 2>{}, y - 1);
-                estage(std::integral_constant<int, NRS + 3>{}, y - 1);
+                if constexpr (NQ < NRS + 3) estage(std::integral_constant<int, NRS + 2>{}, y - 1, std::integral_constant<bool, SRA>{}, ea);
+                estage(std::integral_constant<int, NRS + 3>{}, y - 1, std::integral_constant<bool, SRA>{}, ea);
             }
           }
         } else if (y > yb) {
@@ -1509,7 +1588,7 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
     }
     if constexpr (OVL) {  // the segment's last row: nothing is kept across segments
         auto dr = [&](auto sc) __attribute__((always_inline)) {
-            if constexpr (decltype(sc)::value <= NRS + 3) estage(sc, ye - 1);
+            if constexpr (decltype(sc)::value <= NRS + 3) estage(sc, ye - 1, std::false_type{}, a);
         };
         dr(std::integral_constant<int, 0>{}); dr(std::integral_constant<int, 1>{}); dr(std::integral_constant<int, 2>{});
         dr(std::integral_constant<int, 3>{}); dr(std::integral_constant<int, 4>{}); dr(std::integral_constant<int, 5>{});
@@ -1725,6 +1804,21 @@ static hipError_t launch_bm2_side(const Bm2Args &a, hipStream_t st) {
     // The SAD1 kernels (ABS) are measured fastest on the full grid (C1: 14.9 us at two thirds, 13.6 us
     // full; tools/c1_grid.sh), so the rule applies to the pair / SSD layouts only.
     if (small_grid && !ABS && T < grid * (2L * R + 1) && blocks_per_cu[dev] >= 3) grid = (long)num_cu[dev] * (blocks_per_cu[dev] * 2 / 3);
+    // in_flight handles, one-wave blocks: two thirds of the residency.  A launch that shares the device with two others
+    // gains nothing from a block per resident slot, and every block pays a (2R+1)-row segment start for its rows (C2:
+    // about 20 rows behind a 9-row start at 3072 blocks).  Parent library, three frames in flight, grids of 1, 2/3,
+    // 1/2, 1/3 of the residency (profiles/sref_ab.txt): C2 44.5k / 46.0k / 46.8k / 45.3k Mpix/s, C4 22.4k / 22.9k /
+    // 21.7k / 22.5k, C2r 23.1k / 23.3k / 23.0k / 22.9k, C1 33.2k / 36.6k / 37.7k and 24.8k / 35.9k; half loses on C4.
+    // The two- and four-wave blocks (6 and 4 per CU) keep the full grid: C5 20.57k / 20.55k / 20.29k / 16.9k,
+    // C3 7.18k / 7.25k / 7.26k / 6.41k.  Lone-frame handles keep the full grid.  DSX_FLIGHT_GRID=0 disables.
+    static const bool flight_grid = [] {
+        const char *e = getenv("DSX_FLIGHT_GRID");
+        return !(e && *e == '0');
+    }();
+    if (flight_grid && a.in_flight && NW == 1 && blocks_per_cu[dev] >= 3) {
+        const long g23 = (long)num_cu[dev] * (blocks_per_cu[dev] * 2 / 3);
+        if (g23 < grid) grid = g23;
+    }
     if (a.grid_override > 0) grid = a.grid_override;
     if (grid > T) grid = T;
     if (grid < 1) grid = 1;

@@ -52,6 +52,7 @@ struct Bm2Args {
     int16_t *out_dR;       // right pass output
     void *vol;             // side 2 output [H][W][Dp]
     uint64_t *timeline;    // debug (DSX_TIMELINE env): per block {start, end, hw_id, xcc_id}
+    int in_flight;         // host only: the handle's launches overlap others on the device (launch_bm2_side's grid)
 };
 
 struct VolArgs {
