@@ -92,6 +92,29 @@ constexpr bool kRowstepDivq = DSX_ROWSTEP_DIVQ;          // pair layout, left pa
 constexpr bool kRowstepMerge = DSX_ROWSTEP_MERGE;  // one load and one 16-B store per staged row
 constexpr bool kRowstepAtid = DSX_ROWSTEP_ATID;
 constexpr bool kRowstepKey2 = DSX_ROWSTEP_KEY2;
+// Segment-start forms (the code between kernel entry and a segment's first row step), each behind its own switch
+// for an A/B build; =0 restores the previous form.
+// -DDSX_SEGSTART_AHEAD=0: the transposed init's SAD loop reads chunk q + 1's LDS words in front of chunk q's SADs
+// (two register sets; only a row group's first chunk waits with a full drain) instead of one drain per read.
+// -DDSX_SEGSTART_BATCH=0: the transposed init's row loads of the unaligned-dword copy up to R = 4 are issued in one
+// batch ahead of the transposes, all 2R+1 rows and unconditionally (rows past 2R are compile-time zeros), instead
+// of one global round trip per row group.
+// -DDSX_SEGSTART_SPART=1 switches ON the block's two partition words through scalar loads issued at kernel entry, in
+// front of the invalid-band fill and the LR key reset, instead of two vector loads behind them; off by default: alone
+// it ran the C2 step 0.11 us slower than the parent (44.44 against 44.33 us, spread 0.07), and next to the other two
+// it was within the spread (43.46 against 43.54 us; DESIGN 4.4, profiles/segstart_ab.txt).
+#ifndef DSX_SEGSTART_AHEAD
+#define DSX_SEGSTART_AHEAD 1
+#endif
+#ifndef DSX_SEGSTART_BATCH
+#define DSX_SEGSTART_BATCH 1
+#endif
+#ifndef DSX_SEGSTART_SPART
+#define DSX_SEGSTART_SPART 0
+#endif
+constexpr bool kSegstartAhead = DSX_SEGSTART_AHEAD;
+constexpr bool kSegstartBatch = DSX_SEGSTART_BATCH;
+constexpr bool kSegstartSpart = DSX_SEGSTART_SPART;
 
 #include <algorithm>
 #include <cstdio>
@@ -572,6 +595,12 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
         constexpr int TPG = rnd16(NJ4 * 32);   // pair entries of a group (8 B each)
         constexpr int RG = rnd16(NC4 * 16);     // reference dwords of a group
         static_assert(NGR * (TPG + RG) <= G::SMEM, "transposed init rows must fit the block's LDS");
+        // IBT: the groups unrolled, so the row tests are compile-time and no load sits under a branch, and every
+        // row's loads (3 per row, 27 at R = 4; the accumulators are not live yet) issued in front of the first
+        // transpose, pinned with sched_barrier(0): the segment start waits for one global round trip instead of one
+        // per group.  Unaligned-dword copy up to R = 4 outside the volume and LR passes; the others gain scratch
+        // with it (with group g + 1's loads in front of group g's transposes as well: DESIGN 4.4) and keep the loop.
+        constexpr bool IBT = kSegstartBatch && FAST && R <= 4 && SIDE != 2 && SIDE != 3;
         block_sync<NW>();
         // byte loader in the FAST layout for both paths: w = bytes of entries 3, 2, 1, 0 (byte k =
         // entry 3 - k: positions PB - 4 tj - 3 .. PB - 4 tj), e = entry 4, rf = 4 reference bytes
@@ -580,7 +609,17 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
             const uint8_t *srow = a.src + fin + (long)yy * stride;
             const uint8_t *rrow = a.ref + fin + (long)yy * stride;
             const int tj = min(tid, NJ4 - 1), tr = min(tid, NC4 - 1);
-            if constexpr (FAST) {
+            if constexpr (IBT) {
+                // batched loads: wave-uniform row bases pinned to SGPRs and the lane's part as an unsigned 32-bit
+                // offset (ofs_s >= 1, ofs_r >= 0 by the segment's FAST test), as in ld: no 64-bit address pair per load
+                const uint8_t *sb_ = srow, *rb_ = rrow;
+                asm("" : "+s"(sb_));
+                asm("" : "+s"(rb_));
+                gu8 *ps = (gu8 *)sb_ + ofs_s;
+                w = *reinterpret_cast<gu32 *>(ps);
+                e = ps[-1];
+                rf = *reinterpret_cast<gu32 *>((gu8 *)rb_ + ofs_r);
+            } else if constexpr (FAST) {
                 const uint8_t *pp = srow + PB - 4 * tj - 3;
                 w = *reinterpret_cast<const uint32_t *>(pp);
                 e = pp[-1];
@@ -597,9 +636,8 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
                 rf = v;
             }
         };
-#pragma unroll 1
-        for (int g = 0; g < NGR; ++g) {
-            uint32_t w[4], e[4], rf[4];
+        // a group's 4 rows, loaded (rows past 2R are zero) ...
+        auto ildg = [&](int g, uint32_t(&w)[4], uint32_t(&e)[4], uint32_t(&rf)[4]) __attribute__((always_inline)) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 if (4 * g + r <= 2 * R) {
@@ -610,6 +648,9 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
                     rf[r] = 0;
                 }
             }
+        };
+        // ... and transposed into the group's LDS rows
+        auto itrg = [&](int g, const uint32_t(&w)[4], const uint32_t(&e)[4], const uint32_t(&rf)[4]) __attribute__((always_inline)) {
             // P(entry q) = {w0.byte(3-q), w1.byte(3-q), w2.byte(3-q), w3.byte(3-q)}, q = 0..3
             uint32_t P[5];
 #pragma unroll
@@ -640,6 +681,21 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
                 }
                 *reinterpret_cast<uint4 *>(smem + NGR * TPG + g * RG + 16 * tid) = make_uint4(Rv[0], Rv[1], Rv[2], Rv[3]);
             }
+        };
+        if constexpr (IBT) {
+            uint32_t w[NGR][4], e[NGR][4], rf[NGR][4];
+#pragma unroll
+            for (int g = 0; g < NGR; ++g) ildg(g, w[g], e[g], rf[g]);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int g = 0; g < NGR; ++g) itrg(g, w[g], e[g], rf[g]);
+        } else {
+#pragma unroll 1
+            for (int g = 0; g < NGR; ++g) {
+                uint32_t w[4], e[4], rf[4];
+                ildg(g, w, e, rf);
+                itrg(g, w, e, rf);
+            }
         }
         block_sync<NW>();
         // this lane's pair entry for column c: TP_g[d0 + NC - 1 - c] (8-B aligned); groups in a
@@ -649,6 +705,63 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
         uint32_t ae[NC], ao[NC];
 #pragma unroll
         for (int c = 0; c < NC; ++c) ae[c] = ao[c] = 0;
+        // IAH: chunk q + 1's reads (4 pair entries and the broadcast reference dwords) issued in front of chunk q's
+        // SADs, two register sets pinned with sched_barrier(0) as AHD does in the row loop: only a group's first
+        // chunk waits with a full drain.  Left to the scheduler, every read sits directly in front of its use
+        // (18 drains per group at R = 4, the wave idle on LDS latency).
+        // The R >= 6 builds (88 and more accumulators) gain scratch with it and keep the one-set loop.
+        constexpr bool IAH = kSegstartAhead && R <= 5;
+        if constexpr (IAH) {
+#pragma unroll 1
+            for (int g = 0; g < NGR; ++g) {
+                uint32_t rv[2][4], p0[2][4], p1[2][4];
+                auto ird = [&](auto qc) __attribute__((always_inline)) {
+                    constexpr int q = decltype(qc)::value, c0 = 4 * q, t = q & 1;
+                    const uint4 rr = *reinterpret_cast<const uint4 *>(smem + NGR * TPG + g * RG + 4 * c0);  // broadcast
+                    rv[t][0] = rr.x; rv[t][1] = rr.y; rv[t][2] = rr.z; rv[t][3] = rr.w;
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        if (c0 + c < NC) {
+                            if constexpr (ABS) {
+                                p0[t][c] = *reinterpret_cast<const uint32_t *>(tb + g * TPG + (NC - 1 - c0 - c) * 8);
+                            } else {
+                                const uint2 pr = *reinterpret_cast<const uint2 *>(tb + g * TPG + (NC - 1 - c0 - c) * 8);
+                                p0[t][c] = pr.x;
+                                p1[t][c] = pr.y;
+                            }
+                        }
+                    }
+                };
+                auto isad = [&](auto qc) __attribute__((always_inline)) {
+                    constexpr int q = decltype(qc)::value, c0 = 4 * q, t = q & 1;
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        if (c0 + c < NC) {
+                            ae[c0 + c] = __builtin_amdgcn_sad_u8(rv[t][c], p0[t][c], ae[c0 + c]);
+                            if constexpr (!ABS) ao[c0 + c] = __builtin_amdgcn_sad_u8(rv[t][c], p1[t][c], ao[c0 + c]);
+                        }
+                    }
+                };
+                auto ichunk = [&](auto qc) __attribute__((always_inline)) {
+                    constexpr int q = decltype(qc)::value;
+                    if constexpr (q < NC4) {
+                        __builtin_amdgcn_sched_barrier(0);
+                        if constexpr (q + 1 < NC4) ird(std::integral_constant<int, q + 1>{});
+                        __builtin_amdgcn_sched_barrier(0);
+                        isad(qc);
+                    }
+                };
+                ird(std::integral_constant<int, 0>{});
+                ichunk(std::integral_constant<int, 0>{}); ichunk(std::integral_constant<int, 1>{});
+                ichunk(std::integral_constant<int, 2>{}); ichunk(std::integral_constant<int, 3>{});
+                ichunk(std::integral_constant<int, 4>{}); ichunk(std::integral_constant<int, 5>{});
+                ichunk(std::integral_constant<int, 6>{}); ichunk(std::integral_constant<int, 7>{});
+                ichunk(std::integral_constant<int, 8>{}); ichunk(std::integral_constant<int, 9>{});
+                ichunk(std::integral_constant<int, 10>{}); ichunk(std::integral_constant<int, 11>{});
+                static_assert(NC4 <= 12, "column chunks of the transposed init");
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        } else {
 #pragma unroll 1
         for (int g = 0; g < NGR; ++g) {
 #pragma unroll
@@ -670,6 +783,7 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
                     }
                 }
             }
+        }
         }
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
@@ -1613,6 +1727,17 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((SSD &&
     uint64_t t_prev = 0;
     uint64_t nsteps = 0;
 #endif
+    // SPART: the block's partition words through the scalar unit, issued here so that their latency lies under
+    // the fill and reset loops below (the table is written by the host before the launch: read-only here).  Up to
+    // R = 5: two R >= 6 builds at their register budget gain scratch with the two words held across those loops.
+    constexpr bool SPART = kSegstartSpart && R <= 5;
+    int sp0 = 0, sp1 = 0;
+    if constexpr (SPART) {
+        typedef const __attribute__((address_space(4))) int ci32;
+        ci32 *pp = (ci32 *)((uintptr_t)a.part + 4 * (uintptr_t)blockIdx.x);
+        sp0 = pp[0];
+        sp1 = pp[1];
+    }
 
     // ---- left pass: columns of strips that lie entirely in the invalid band ----
     if ((side == 0 || side == 3 || side == 4) && (a.out_fixed || a.out_float)) {
@@ -1647,7 +1772,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((SSD &&
 
     // ---- work partition (host-computed, bm2_partition): block b owns linear (frame, strip, row)
     // units [part[b], part[b+1]); nframes * H * W < 2^31 (host check)
-    const int lin0 = a.part[blockIdx.x], lin1 = a.part[blockIdx.x + 1];
+    const int lin0 = SPART ? sp0 : a.part[blockIdx.x], lin1 = SPART ? sp1 : a.part[blockIdx.x + 1];
     constexpr bool lr_on = SIDE == 3;  // left pass that also builds the right-view winners
     int qcur = -1;
     int pe[3];  // rows done at which the priority drops (progress bands pt1..pt3 of 256)

@@ -12,7 +12,9 @@ loop of an instantiation (the unaligned-dword copy and the clamped-byte copy of 
     cycles per wave-instruction for conflict-free accesses; a store's cycles are those of moving its
     address and data dwords to the LDS).  Static counts over every block of the loop, the branches a
     benchmark step does not take included (odd-D overwrite, uniqueness re-reads, edge overwrites);
-  * the kernel's VGPRs, scratch bytes and LDS bytes per block (Geo in dsx_bm.hip, restated here).
+  * the kernel's VGPRs, scratch bytes and LDS bytes per block (Geo in dsx_bm.hip, restated here);
+  * a segment-start table (segstart_report below): LDS drains of the init SAD loop, loads, vmcnt waits and global
+    round trips of the init rows, memory waits in front of the segment loop.
 
 It reports; it gates nothing.
 
@@ -155,6 +157,92 @@ def report(asm, name, out):
             out(w)
 
 
+def segstart_report(asm, name, out):
+    """Segment-start table of one instantiation: what a block waits for between kernel entry and a segment's
+    first row step.  Per copy of bm2_segment (unaligned-dword, clamped):
+
+      * the init SAD loop - the innermost loop outside the row loops that holds v_sad_* and LDS reads and no global
+        memory operation (one iteration per row group of the transposed init, per row of the row-by-row init): its
+        s_waitcnt lgkmcnt(0) (full LDS drains) and all lgkmcnt waits per iteration;
+      * the init row loads - the blocks from which that loop is reached without crossing a global store (the previous
+        segment's row loop) or the head of the segment loop: global loads, vmcnt waits, and the global round trips they add up to
+        (a loop over row groups that holds loads: one per group; straight-line code: the runs of loads that a vmcnt
+        wait separates from the next load);
+      * the memory waits (vmcnt / lgkmcnt) in front of the segment loop, from kernel entry.
+    """
+    r, ssd, nw, side, abs_ = BENCH_KERNELS[name]
+    sym = symbol(r, ssd, nw, side, abs_)
+    body = function_body(asm, sym)
+    bl = blocks(body)
+    loops, _ = row_loops(bl)
+    ln = lines_of(body)
+    index = {lab: i for i, (lab, _, _) in enumerate(bl)}
+    ops_of = {}
+    for lab, op, arg in ln:
+        ops_of.setdefault(lab, []).append((op, arg))
+    in_row = set()
+    for i, j in loops:
+        in_row |= set(range(i, j + 1))
+    back = sorted({(index[t], j) for j, (_, _, tg) in enumerate(bl) for t in tg if t in index and index[t] <= j})
+    rng_ops = lambda i, j: [o for k in range(i, j + 1) for o in ops_of.get(bl[k][0], [])]  # noqa: E731
+    has = lambda ops, p: any(op.startswith(p) for op, _ in ops)  # noqa: E731
+    vg, scratch, _ = meta(asm, sym)
+    out(f"{name} {kernel_label(r, ssd, nw, side, abs_)} segment start: VGPRs {vg}, scratch {scratch} B")
+    if loops:
+        seg0 = min(i for i, j in back if any(i <= a and b <= j for a, b in loops))
+        waits = [f"{op} {arg}" for k in range(seg0) for op, arg in ops_of.get(bl[k][0], [])
+                 if op == "s_waitcnt" and ("vmcnt" in arg or "lgkmcnt" in arg)]
+        out(f"  kernel entry to the segment loop ({bl[seg0][0]}): {len(waits)} memory waits: {'; '.join(waits) or '-'}")
+    # successors in the control flow (fall-through unless the block ends in s_branch)
+    succ = {}
+    for k, (lab, ops, tg) in enumerate(bl):
+        s = {index[t] for t in tg if t in index}
+        if k + 1 < len(bl) and not (ops and ops[-1] == "s_branch"):
+            s.add(k + 1)
+        succ[k] = s
+    pred = {}
+    for k, s in succ.items():
+        for t in s:
+            pred.setdefault(t, set()).add(k)
+    ngr = (2 * r + 1 + 3) // 4
+    for i, j in back:
+        ops = rng_ops(i, j)
+        if (i in in_row or not has(ops, "v_sad_") or not has(ops, "ds_read") or has(ops, "global_")
+                or any((a, b) != (i, j) and i <= a and b <= j for a, b in back)):
+            continue
+        n = lambda p: sum(1 for op, _ in ops if op.startswith(p))  # noqa: E731
+        full = sum(1 for op, arg in ops if op == "s_waitcnt" and "lgkmcnt(0)" in arg)
+        anyw = sum(1 for op, arg in ops if op == "s_waitcnt" and "lgkmcnt" in arg)
+        out(f"  init SAD loop {bl[i][0]}: v_sad {n('v_sad_')}, LDS reads {n('ds_read')}, s_waitcnt lgkmcnt(0) {full} "
+            f"of {anyw} lgkmcnt waits per iteration")
+        # backwards from the loop, not through global stores, row loops or the loop itself
+        reg, todo = set(), [p for p in pred.get(i, ()) if not i <= p <= j]
+        while todo:
+            k = todo.pop()
+            if k in reg or k in in_row or (loops and k <= seg0) or has(ops_of.get(bl[k][0], []), "global_store") or has(ops_of.get(bl[k][0], []), "global_atomic"):
+                continue
+            reg.add(k)
+            todo.extend(pred.get(k, ()))
+        rops = [o for k in sorted(reg) for o in ops_of.get(bl[k][0], [])]
+        loads = sum(1 for op, _ in rops if op.startswith("global_load"))
+        vmw = [arg for op, arg in rops if op == "s_waitcnt" and "vmcnt" in arg]
+        looped = any(all(k in reg for k in range(a, b + 1)) and has(rng_ops(a, b), "global_load") for a, b in back)
+        if looped:
+            trips = f"{ngr} (a loop over the {ngr} row groups holds the loads)" if has(rops, "v_perm") else "one per loop iteration"
+        else:
+            t, pending, waited = 0, False, True
+            for k in sorted(reg):
+                for op, arg in ops_of.get(bl[k][0], []):
+                    if op.startswith("global_load"):
+                        if waited:
+                            t, waited = t + 1, False
+                        pending = True
+                    elif op == "s_waitcnt" and "vmcnt" in arg and pending:
+                        waited = True
+            trips = str(t)
+        out(f"    init row loads in front of it: global loads {loads}, vmcnt waits {len(vmw)}, global round trips {trips}")
+
+
 def main(argv):
     src = os.path.join(ROOT, "depthestimation_amd", "csrc", "dsx_bm.hip")
     tag = None
@@ -184,6 +272,7 @@ def main(argv):
         asm[r] = open(os.path.join(tmp, f"r{r}.s")).read()
     for n in names:
         report(asm[BENCH_KERNELS[n][0]], n, out)
+        segstart_report(asm[BENCH_KERNELS[n][0]], n, out)
 
 
 if __name__ == "__main__":
