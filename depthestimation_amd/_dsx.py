@@ -21,7 +21,8 @@ DSX_EHIP = -2
 DSX_ECOMM = -3
 DSX_ENOMEM = -4
 
-COST = {"sad": 0, "ssd": 1, "bt": 2}  # include/dsx.h DSX_COST_*
+COST = {"sad": 0, "ssd": 1, "bt": 2, "census9x7": 3, "census5x5": 4}  # include/dsx.h DSX_COST_*
+CENSUS_WINDOW = {"census9x7": (9, 7), "census5x5": (5, 5)}  # (wx, wy) of the census costs
 FLOAT_MODE = {"fixed": 0, "parabola": 1}
 PATH = {"fused": 0, "volume": 1}
 # SGM path sets by the reference's sgbm_mode names (stereo_core.py:55-61), include/dsx.h DSX_AGG_*
@@ -40,7 +41,7 @@ EXPORTS = (
     "dsx_fill_nearest_footprint", "dsx_fill_nearest_workspace_bytes", "dsx_fill_nearest_device",
     "dsx_postprocess_device", "dsx_resize_area_table", "dsx_resize_area_device",
     "dsx_default_prefilter", "dsx_check_prefilter", "dsx_set_prefilter", "dsx_prefilter_device",
-    "dsx_texture_sum_device",
+    "dsx_texture_sum_device", "dsx_census_device",
 )
 
 
@@ -140,6 +141,7 @@ def _bind(lib):
         "dsx_set_prefilter": (ctypes.c_int, [vp, F]),
         "dsx_prefilter_device": (ctypes.c_int, [vp, i32, i32, i64, F, vp, i64, vp]),
         "dsx_texture_sum_device": (ctypes.c_int, [vp, i32, i32, i64, i32, i32, vp, vp]),
+        "dsx_census_device": (ctypes.c_int, [vp, i32, i32, i64, i32, vp, vp]),
         "dsx_version": (ctypes.c_int, []),
         "dsx_device_count": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)]),
         "dsx_default_params": (None, [P]),

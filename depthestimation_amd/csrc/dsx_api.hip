@@ -82,8 +82,13 @@ int sgm_set(int mode, const int **set) {
 
 int bt_ftzero(const dsx_params &p) { return (p.prefilter_cap > 15 ? p.prefilter_cap : 15) | 1; }
 
+bool is_census(int cost) { return cost == DSX_COST_CENSUS9X7 || cost == DSX_COST_CENSUS5X5; }
+// costs that exist only as a volume (no fused pass, no right-view pass): BT and census
+bool volume_only(int cost) { return cost == DSX_COST_BT || is_census(cost); }
+
 uint64_t max_cost(const dsx_params &p) {
     const uint64_t n = (uint64_t)p.block_size * p.block_size;
+    if (is_census(p.cost)) return n * (p.cost == DSX_COST_CENSUS9X7 ? 62ull : 24ull);  // Hamming bits per pixel
     if (p.cost == DSX_COST_BT) return n * (uint64_t)(2 * bt_ftzero(p) + 63);  // oracle/bt_cost.py max_cost_bt
     return n * (p.cost == DSX_COST_SSD ? 255ull * 255ull : 255ull);
 }
@@ -93,8 +98,8 @@ int check(const dsx_params *p) {
     if (p->block_size < 1 || p->block_size > 15 || (p->block_size & 1) == 0)
         return fail(DSX_EINVAL, "block_size must be odd and in [1, 15]");
     if (p->num_disp < 1 || p->num_disp > 512) return fail(DSX_EINVAL, "num_disp must be in [1, 512]");
-    if (p->cost != DSX_COST_SAD && p->cost != DSX_COST_SSD && p->cost != DSX_COST_BT)
-        return fail(DSX_EINVAL, "cost must be SAD (0), SSD (1) or BT (2)");
+    if (p->cost != DSX_COST_SAD && p->cost != DSX_COST_SSD && p->cost != DSX_COST_BT && !is_census(p->cost))
+        return fail(DSX_EINVAL, "cost must be SAD (0), SSD (1), BT (2), CENSUS9X7 (3) or CENSUS5X5 (4)");
     if (p->cost == DSX_COST_BT && (p->prefilter_cap < 1 || p->prefilter_cap > 63))
         return fail(DSX_EINVAL, "prefilter_cap must be in [1, 63]");
     if (p->sgbm_post != 0 && p->sgbm_post != 1) return fail(DSX_EINVAL, "sgbm_post must be 0 or 1");
@@ -119,7 +124,7 @@ int check(const dsx_params *p) {
         if (p->aggregation != DSX_AGG_SGBM_3WAY && p->aggregation != DSX_AGG_HH4 && p->aggregation != DSX_AGG_SGBM &&
             p->aggregation != DSX_AGG_HH)
             return fail(DSX_EINVAL, "aggregation must be 0, 3 (sgbm_3way), 4 (hh4), 5 (sgbm) or 8 (hh)");
-        if (p->cost == DSX_COST_SSD) return fail(DSX_EINVAL, "SGM aggregation runs on SAD or BT block costs");
+        if (p->cost == DSX_COST_SSD) return fail(DSX_EINVAL, "SGM aggregation runs on SAD, BT or census block costs");
         if (p->num_disp > 256) return fail(DSX_EINVAL, "SGM aggregation supports num_disp <= 256");
         if (p->p1 > 65535 || p->p2 > 65535 || (p->p1 > 0 && p->p2 > 0 && p->p2 < p->p1))
             return fail(DSX_EINVAL, "SGM penalties must satisfy 0 < P1 <= P2 <= 65535");
@@ -138,6 +143,9 @@ int check_prefilter(const dsx_params *p, const dsx_prefilter *f) {
         return fail(DSX_EINVAL, "prefilter type must be NONE (0), XSOBEL (1) or MEAN (2)");
     if (f->texture_threshold < 0 || f->texture_threshold > 65535)
         return fail(DSX_EINVAL, "texture_threshold must be in [0, 65535]");
+    if (p && is_census(p->cost) && (f->type != DSX_PREFILTER_NONE || f->texture_threshold > 0))
+        return fail(DSX_EINVAL, "census ranks intensities itself: a census cost cannot be combined with a prefilter "
+                                "or a texture threshold");
     if (f->type == DSX_PREFILTER_NONE) {
         if (f->texture_threshold > 0)
             return fail(DSX_EINVAL, "texture_threshold > 0 needs a prefilter (the cap has no meaning on raw images)");
@@ -192,6 +200,8 @@ struct dsx_handle {
     size_t vol_bytes = 0;
     void *btWs = nullptr;  // DSX_COST_BT: prep records of both views | horizontal sums
     size_t btWsBytes = 0;
+    void *censusWs = nullptr;  // census costs: the code plane of the left view | of the right view
+    size_t censusWsBytes = 0;
     int16_t *postIn = nullptr;  // sgbm_post: the matcher's int16 maps (postFrames frames)
     void *postWs = nullptr;     // sgbm_post: median | speckle components
     size_t postInBytes = 0, postWsBytes = 0;
@@ -230,6 +240,9 @@ void free_buffers(dsx_handle *h) {
     (void)hipFree(h->vol);
     (void)hipFree(h->btWs);
     h->btWs = nullptr;
+    (void)hipFree(h->censusWs);
+    h->censusWs = nullptr;
+    h->censusWsBytes = 0;
     (void)hipFree(h->postIn);
     (void)hipFree(h->postWs);
     h->postIn = nullptr;
@@ -303,7 +316,7 @@ int ensure_buffers(dsx_handle *h, int H, int W, bool host_staging, int nframes =
         DSX_HIP(hipMalloc(&h->dFloat, n * 4));
         h->stagingBytes = n * (1 + 1 + 2 + 4);
     }
-    const bool fused = h->p.path == DSX_PATH_FUSED && !h->p.aggregation && h->p.cost != DSX_COST_BT;
+    const bool fused = h->p.path == DSX_PATH_FUSED && !h->p.aggregation && !volume_only(h->p.cost);
     const bool lr_any = h->p.disp12_max_diff >= 0 || h->p.lr_form == DSX_LR_FORM_SGBM;  // OpenCV's form: always on
     if (lr_any && fused && h->lrFrames < nframes) {
         (void)hipFree(h->lrKeys);
@@ -332,6 +345,9 @@ int ensure_buffers(dsx_handle *h, int H, int W, bool host_staging, int nframes =
         return rc;
     if (!fused && (rc = grow(h->vol, h->vol_bytes, n * h->g.Dp * cbytes))) return rc;
     if (bt && (rc = grow(h->btWs, h->btWsBytes, dsx::bt_workspace(H, W, h->g.Dp)))) return rc;
+    if (is_census(h->p.cost) &&
+        (rc = grow(h->censusWs, h->censusWsBytes, 2 * n * dsx::census_code_bytes(h->p.cost))))
+        return rc;
     if (h->p.sgbm_post && h->postFrames < nframes) {
         (void)hipFree(h->postIn);
         h->postIn = nullptr;
@@ -582,9 +598,17 @@ int run_prefilter(dsx_handle *h, const void *&dL, const void *&dR, int H, int W,
     return DSX_OK;
 }
 
+// rows per census_volume segment: DSX_CENSUS_SEG = 16 | 32 | 64 (the sweep of DESIGN 4.3e), else the default
+int census_seg() {
+    const char *e = getenv("DSX_CENSUS_SEG");
+    const int v = e ? atoi(e) : 0;
+    return v == 16 || v == 32 || v == 64 ? v : 0;
+}
+
 int run_right_pass(dsx_handle *h, const void *dL, const void *dR, int H, int W, int64_t stride, int16_t *out,
                    hipStream_t st) {
-    if (h->p.cost == DSX_COST_BT) return fail(DSX_EINVAL, "the right-view map is a block-matching (SAD/SSD) pass");
+    if (volume_only(h->p.cost))
+        return fail(DSX_EINVAL, "the right-view map is a block-matching (SAD/SSD) pass");
     const bool pf = h->pf.type != DSX_PREFILTER_NONE;
     ScratchRecord rec_(h, st, false);
     if (pf) {
@@ -615,7 +639,8 @@ int run(dsx_handle *h, const void *dL, const void *dR, int H, int W, int64_t str
     const bool bt = h->p.cost == DSX_COST_BT;  // BT costs exist only as a volume
     // sgbm_post: the matcher writes int16 maps into postIn, the tail then writes the outputs
     void *const finalFixed = outFixed, *const finalFloat = outFloat;
-    const bool fused = h->p.path == DSX_PATH_FUSED && !h->p.aggregation && !bt;
+    const bool census = is_census(h->p.cost);  // so do census costs
+    const bool fused = h->p.path == DSX_PATH_FUSED && !h->p.aggregation && !volume_only(h->p.cost);
     const bool lr_sg = h->p.lr_form == DSX_LR_FORM_SGBM;  // OpenCV's LR form (always on)
     const bool pf = h->pf.type != DSX_PREFILTER_NONE;  // the filtered images are handle scratch too
     const bool scratch = h->p.disp12_max_diff >= 0 || lr_sg || !fused || h->p.sgbm_post || pf;
@@ -749,6 +774,34 @@ int run(dsx_handle *h, const void *dL, const void *dR, int H, int W, int64_t str
                 b.padv = pad_value(h);
                 DSX_LAUNCH(h, "bt_hsum", st, dsx::launch_bt_volume(b, 0, st));
                 DSX_LAUNCH(h, "bt_vsum", st, dsx::launch_bt_volume(b, 1, st));
+            } else if (census) {
+                const size_t cb = (size_t)H * W * dsx::census_code_bytes(h->p.cost);
+                dsx::CensusArgs c{};
+                c.src[0] = static_cast<const uint8_t *>(dL) + f * frame_stride;
+                c.src[1] = static_cast<const uint8_t *>(dR) + f * frame_stride;
+                c.stride = stride;
+                c.dst[0] = h->censusWs;
+                c.dst[1] = static_cast<uint8_t *>(h->censusWs) + cb;
+                c.nviews = 2;
+                c.H = H;
+                c.W = W;
+                c.window = h->p.cost;
+                c.out64 = h->p.cost == DSX_COST_CENSUS9X7;
+                DSX_LAUNCH(h, "census_transform", st, dsx::launch_census_transform(c, st));
+                dsx::CensusVolArgs v{};
+                v.codeL = c.dst[0];
+                v.codeR = c.dst[1];
+                v.vol = h->vol;
+                v.H = H;
+                v.W = W;
+                v.m = h->p.min_disp;
+                v.D = h->p.num_disp;
+                v.Dp = h->g.Dp;
+                v.R = radius;
+                v.window = h->p.cost;
+                v.seg = census_seg();
+                v.padv = pad_value(h);
+                DSX_LAUNCH(h, "census_volume", st, dsx::launch_census_volume(v, st));
             } else {
                 dsx::Bm2Args a = base_args(h, H, W, stride);
                 a.side = dsx::SIDE_VOLUME;
@@ -870,6 +923,7 @@ int set_error(int code, const std::string &msg) { return fail(code, msg); }
 }  // namespace dsx
 
 static_assert(dsx::kFillInpaint == DSX_FILL_INPAINT && dsx::kFillNearest == DSX_FILL_NEAREST, "fill methods");
+static_assert(dsx::kCensus9x7 == DSX_COST_CENSUS9X7 && dsx::kCensus5x5 == DSX_COST_CENSUS5X5, "census windows");
 static_assert(dsx::kPrefNone == DSX_PREFILTER_NONE && dsx::kPrefXsobel == DSX_PREFILTER_XSOBEL &&
                   dsx::kPrefMean == DSX_PREFILTER_MEAN, "prefilter types");
 static_assert(dsx::kNearestFused == DSX_NEAREST_FUSED && dsx::kNearestStep == DSX_NEAREST_STEPWISE &&
@@ -947,6 +1001,9 @@ int dsx_set_params(dsx_handle *h, const dsx_params *p) {
     if (h->pf.type != DSX_PREFILTER_NONE && p->cost == DSX_COST_BT)
         return fail(DSX_EINVAL, "the handle has a prefilter set (dsx_set_prefilter): cost BT filters for itself; "
                                 "switch the prefilter off first");
+    if ((h->pf.type != DSX_PREFILTER_NONE || h->pf.texture_threshold > 0) && is_census(p->cost))
+        return fail(DSX_EINVAL, "the handle has a prefilter set (dsx_set_prefilter): census ranks intensities "
+                                "itself; switch the prefilter off first");
     DSX_HIP(hipSetDevice(h->device));
     DSX_HIP(hipStreamSynchronize(h->stream));
     h->p = *p;
@@ -1028,6 +1085,26 @@ int dsx_texture_sum_device(const void *d_pref, int32_t H, int32_t W, int64_t str
     t.cap = cap;
     t.out_sum = static_cast<uint16_t *>(d_out_u16);
     DSX_HIP(dsx::launch_texture(t, static_cast<hipStream_t>(hip_stream)));
+    return DSX_OK;
+}
+
+int dsx_census_device(const void *d_img, int32_t H, int32_t W, int64_t stride_bytes, int32_t cost, void *d_out_u64,
+                      void *hip_stream) {
+    g_err.clear();
+    if (!d_img || !d_out_u64) return fail(DSX_EINVAL, "NULL image or output");
+    if (!is_census(cost)) return fail(DSX_EINVAL, "cost must be CENSUS9X7 (3) or CENSUS5X5 (4)");
+    int rc = check_shape(H, W, stride_bytes);
+    if (rc) return rc;
+    dsx::CensusArgs c{};
+    c.src[0] = static_cast<const uint8_t *>(d_img);
+    c.stride = stride_bytes;
+    c.dst[0] = d_out_u64;
+    c.nviews = 1;
+    c.H = H;
+    c.W = W;
+    c.window = cost;
+    c.out64 = 1;
+    DSX_HIP(dsx::launch_census_transform(c, static_cast<hipStream_t>(hip_stream)));
     return DSX_OK;
 }
 
@@ -1456,7 +1533,7 @@ int dsx_process_pair_device(dsx_handle *h, const void *dL, const void *dR, int32
         a.kernel = pp->outlier_kernel;
         // the fused pass's LR check moves into the speckle pass's loads (no lr_fixup launch) when that
         // pass is the two-launch form and the matcher is the fused pass with a check
-        const bool fusedp = h->p.path == DSX_PATH_FUSED && !h->p.aggregation && h->p.cost != DSX_COST_BT &&
+        const bool fusedp = h->p.path == DSX_PATH_FUSED && !h->p.aggregation && !volume_only(h->p.cost) &&
                             !h->p.sgbm_post;
         const bool lrc = h->p.lr_form == DSX_LR_FORM_SGBM || h->p.disp12_max_diff >= 0;
         // a texture threshold masks the checked map: the fix-up runs in run(), then the mask
@@ -1551,7 +1628,7 @@ int dsx_reset_times(dsx_handle *h) {
 
 int dsx_workspace_bytes(dsx_handle *h, int64_t *bytes) {
     if (!h || !bytes) return fail(DSX_EINVAL, "NULL argument");
-    *bytes = (int64_t)(h->stagingBytes + h->pfBytes + h->lrKeysBytes + h->dStarBytes + h->vol_bytes + h->btWsBytes +
+    *bytes = (int64_t)(h->stagingBytes + h->pfBytes + h->lrKeysBytes + h->dStarBytes + h->vol_bytes + h->btWsBytes + h->censusWsBytes +
                        h->postInBytes + h->postWsBytes + h->sgmSBytes + h->sgmLBytes + h->ppDispBytes +
                        h->ppFixedBytes + h->ppWsBytes);
     return DSX_OK;

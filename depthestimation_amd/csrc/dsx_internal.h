@@ -247,6 +247,29 @@ hipError_t launch_bt_prep(const uint8_t *img, int64_t pitch, int H, int W, int f
 // part 0: horizontal sums (bt_hsum), part 1: vertical sums into the volume (bt_vsum)
 hipError_t launch_bt_volume(const BtArgs &a, int part, hipStream_t st);
 
+// Census block costs into K1's volume layout (dsx_census.hip, depthestimation_amd/census.py)
+constexpr int kCensus9x7 = 3, kCensus5x5 = 4;  // DSX_COST_CENSUS*: the window is the cost's name
+constexpr int kCensusSeg = 16;                 // rows per census_volume segment (the sweep of DESIGN.md 4.3e)
+struct CensusArgs {
+    const uint8_t *src[2];  // view v (nviews of them, grid z), row stride `stride` bytes
+    int64_t stride;
+    void *dst[2];           // contiguous H x W codes: u64, or u32 (5x5 with out64 = 0)
+    int nviews, H, W;
+    int window;             // kCensus9x7 | kCensus5x5
+    int out64;
+};
+struct CensusVolArgs {
+    const void *codeL, *codeR;  // census_transform's planes (9x7: u64, 5x5: u32)
+    void *vol;                  // out: [H][W][Dp] u16, pads >= D
+    int H, W, m, D, Dp, R;
+    int window;
+    int seg;                    // rows per segment; 0: kCensusSeg
+    uint32_t padv;
+};
+size_t census_code_bytes(int window);  // bytes per code inside the handle
+hipError_t launch_census_transform(const CensusArgs &a, hipStream_t st);
+hipError_t launch_census_volume(const CensusVolArgs &a, hipStream_t st);
+
 // Rectification (dsx_rectify.hip): gray conversion fused with the fixed-point bilinear remap.
 struct RectArgs {
     const uint8_t *img;  // Hs x Ws x channels (channels 1 or 3, BGR order), row stride in bytes

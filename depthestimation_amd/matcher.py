@@ -80,7 +80,7 @@ def _check_out(t, shape, dtype_name, dev, name):
 
 
 class HipBlockMatcher:
-    """SAD/SSD block matcher running on one HIP device (one handle per thread / GPU)."""
+    """Block matcher (SAD / SSD / BT / census costs) running on one HIP device (one handle per thread / GPU)."""
 
     def __init__(self, min_disp=0, num_disp=128, block_size=5, cost="sad", uniqueness_ratio=10,
                  disp12_max_diff=1, subpixel=True, float_mode="fixed", path="fused", device=0,
@@ -439,6 +439,30 @@ def prefilter_device(img, prefilter_type="xsobel", prefilter_size=9, prefilter_c
     rc = _dsx.lib().dsx_prefilter_device(img.data_ptr(), H, W, img.stride(0), ctypes.byref(f), out.data_ptr(),
                                          out.stride(0), _stream_ptr(stream))
     _dsx.check(rc, "dsx_prefilter_device")
+    return out
+
+
+def census_device(img, cost="census9x7", out=None, stream=None):
+    """The census transform alone on the device (dsx_census_device; host restatement
+    depthestimation_amd/census.py ``census_transform``): ``img`` uint8 H x W HIP tensor (unit column stride,
+    any row stride or offset) -> int64 H x W codes of the window ``cost`` names ('census9x7': 62 bits,
+    'census5x5': 24 bits)."""
+    import torch
+
+    if cost not in _dsx.CENSUS_WINDOW:
+        raise ValueError(f"cost must be one of {list(_dsx.CENSUS_WINDOW)}, got {cost!r}")
+    if img.dtype != torch.uint8 or img.dim() != 2 or not img.is_cuda or img.stride(1) != 1:
+        raise ValueError("img must be a uint8 H x W device tensor with unit column stride")
+    H, W = img.shape
+    if out is None:
+        out = torch.empty((H, W), dtype=torch.int64, device=img.device)
+    elif out.dtype != torch.int64 or out.shape != (H, W) or not out.is_contiguous() or out.device != img.device:
+        raise ValueError("out must be a contiguous int64 H x W tensor on the input's device")
+    if H == 0 or W == 0:
+        return out
+    rc = _dsx.lib().dsx_census_device(img.data_ptr(), H, W, img.stride(0), _dsx.COST[cost], out.data_ptr(),
+                                      _stream_ptr(stream))
+    _dsx.check(rc, "dsx_census_device")
     return out
 
 

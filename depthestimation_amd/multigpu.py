@@ -502,7 +502,7 @@ class BandedStereo:
     """One frame split into horizontal row bands over several GPUs, for latency on large frames
     ("a single 4K frame can alternatively be row-banded with (block-1)/2 halo rows,
     no exchange").  Band i computes output rows [y0, y1) from input rows [y0 - r, y1 + r) clipped
-    to the image, r = block_size // 2 (plus the reach of a prefilter).  Every term of the A5' contract is row-local except the
+    to the image, r = block_size // 2 (plus the reach of a prefilter or a census window).  Every term of the A5' contract is row-local except the
     vertical window, which the halo supplies, and the image's own top / bottom clamp coincides
     with the sub-image's, so the stitched map equals the single-device result bit for bit.
     ``devices`` may repeat a device (several bands on one GPU, e.g. for testing)."""
@@ -521,6 +521,8 @@ class BandedStereo:
         # needs must themselves be computed from real rows (xsobel 1, mean prefilter_size // 2)
         pt = self.matcher_kw.get("prefilter_type", "none")
         self.r += {"none": 0, "xsobel": 1}.get(pt, int(self.matcher_kw.get("prefilter_size", 9)) // 2)
+        # a census code reads ry rows either side of its pixel (9x7: 3, 5x5: 2)
+        self.r += _dsx.CENSUS_WINDOW.get(self.matcher_kw.get("cost", "sad"), (1, 1))[1] // 2
         self._m = [HipBlockMatcher(device=d, **self.matcher_kw) for d in self.devices]
         from concurrent.futures import ThreadPoolExecutor
         self._pool = ThreadPoolExecutor(max_workers=len(self.devices))

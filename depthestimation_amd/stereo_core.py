@@ -7,9 +7,15 @@ include/dsx.h) instead of ``cv2.StereoSGBM_create``, and ``compute_disparity``
 (stereo_core.py:212-232) calls its ``compute`` with the same cv2 contract (int16 x16 -> /16).
 
 Keys added to ``sgbm_params`` (accepted by ``configure_sgbm`` like the reference's own keys):
-  'cost'     : 'sad' | 'ssd' | 'bt'   (block cost; north_star SAD/SSD; 'bt' is OpenCV SGBM's
+  'cost'     : 'sad' | 'ssd' | 'bt' | 'census9x7' | 'census5x5'
+                                      (block cost; north_star SAD/SSD; 'bt' is OpenCV SGBM's
                                        Birchfield-Tomasi pixel cost on the 'prefilter_cap'-clipped
-                                       x-derivative plus intensity, summed over the same block)
+                                       x-derivative plus intensity, summed over the same block; the
+                                       census costs are this build's addition (census.py): the Hamming
+                                       distance of 9x7 (62-bit) or 5x5 (24-bit) rank codes, invariant to
+                                       gain and shading, the usual pixel cost under 'aggregation': 'sgm'
+                                       with 'block_size' 1.  'prefilter_type' and 'texture_threshold' are
+                                       refused with a census cost: census ranks intensities itself)
   'sgbm_post': bool                   (False; True runs cv2.StereoSGBM::compute's own tail on the
                                        int16 map: 3x3 median, then filterSpeckles with
                                        'speckle_window_size' / 'speckle_range' and newVal

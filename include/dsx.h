@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define DSX_VERSION 106 /* additive since 1.0.6 (layouts unchanged): dsx_resize_area_*, dsx_fill_nearest_*,
+#define DSX_VERSION 106 /* additive since 1.0.6 (layouts unchanged): DSX_COST_CENSUS*, dsx_census_device, dsx_resize_area_*, dsx_fill_nearest_*,
                            dsx_postprocess_device,
                            dsx_prefilter, dsx_default_prefilter, dsx_check_prefilter, dsx_set_prefilter,
                            dsx_prefilter_device, dsx_texture_sum_device (matcher prefilter + texture threshold);
@@ -54,6 +54,21 @@ extern "C" {
  * raw intensity >> 2, cv2.StereoSGBM preFilterCap, stereo_core.py:63-75) summed over the same
  * block window; runs on the volume path (K1 replaced by the BT volume, then K2 / SGM). */
 #define DSX_COST_BT 2
+/* Census costs: the Hamming distance between local rank codes, invariant to any monotone intensity change
+ * per window.  An addition of this build (as the prefilter is): parity with nothing outside this
+ * repository is claimed.  The cost's name carries the window wx x wy: 9x7 (62 bits, the usual choice under
+ * SGM) or 5x5 (24 bits).  With cx / cy the replicate clamp, rx = wx / 2, ry = wy / 2:
+ *   code T(I)(x, y): the neighbours (i, j), j from -ry to ry (outer), i from -rx to rx (inner), the centre
+ *       skipped, counted k = 0, 1, ...; bit k = 1 iff I(cx(x+i), cy(y+j)) < I(x, y) (strict); upper bits 0.
+ *   block cost (the A5' window, block_size 1..15; 1 = the per-pixel Hamming cost used with SGM):
+ *       C(x, y, d) = sum over |i|, |j| <= r of popcount(T_L[cy(y+j), cx(x+i)] xor T_R[cy(y+j), cx(x+i-m-d)])
+ *       (the coordinates of the codes are clamped, not the codes' inputs); at most 225 * 62 = 13,950.
+ * Everything after C is unchanged (WTA, uniqueness, both LR forms, sub-pixel, float modes, sgbm_post, SGM).
+ * Like BT, census costs exist only as a volume: a handle with path FUSED runs the volume path (two
+ * launches, census_transform and census_volume, replace K1), dsx_right_map_device returns DSX_EINVAL, and a
+ * prefilter or a texture threshold with a census cost is DSX_EINVAL (census ranks intensities itself). */
+#define DSX_COST_CENSUS9X7 3
+#define DSX_COST_CENSUS5X5 4
 
 #define DSX_FLOAT_FIXED 0    /* out_float = out_fixed / 16 (stereo_core.py:232 contract) */
 #define DSX_FLOAT_PARABOLA 1 /* out_float = continuous parabola vertex (north-star 1e-3 path) */
@@ -91,7 +106,7 @@ typedef struct dsx_params {
     int32_t min_disp;         /* 'min_disp'          (stereo_core.py:17, cv2 minDisparity)    */
     int32_t num_disp;         /* 'num_disp'          (stereo_core.py:18, cv2 numDisparities)  */
     int32_t block_size;       /* 'block_size'        (stereo_core.py:19), odd, 1..15          */
-    int32_t cost;             /* DSX_COST_SAD | DSX_COST_SSD | DSX_COST_BT (build key 'cost')  */
+    int32_t cost;             /* DSX_COST_SAD | _SSD | _BT | _CENSUS9X7 | _CENSUS5X5 (build key 'cost') */
     int32_t uniqueness_ratio; /* 'uniqueness_ratio'  (stereo_core.py:22), 0 disables, <100    */
     int32_t disp12_max_diff;  /* 'disp12_max_diff'   (stereo_core.py:20), <0 disables LR      */
     int32_t subpixel;         /* build key 'subpixel': 1 = 1/16-px parabola, 0 = integer      */
@@ -138,7 +153,7 @@ int dsx_create(int device, const dsx_params *p, dsx_handle **out);
 
 /* Replace the parameters of an existing matcher (configure_sgbm -> _build_sgbm,
  * stereo_core.py:77-123). The parameters are validated first (DSX_EINVAL names the cause and the
- * handle keeps its old set; so does a switch to DSX_COST_BT while a prefilter is set). The next
+ * handle keeps its old set; so does a switch to DSX_COST_BT or a census cost while a prefilter is set). The next
  * call grows every cached device buffer that the new set needs larger (e.g. the SGM buffer with the
  * direction count); a buffer may stay larger than needed. */
 int dsx_set_params(dsx_handle *h, const dsx_params *p);
@@ -190,6 +205,12 @@ int dsx_prefilter_device(const void *d_img, int32_t H, int32_t W, int64_t stride
 int dsx_texture_sum_device(const void *d_pref, int32_t H, int32_t W, int64_t stride_bytes, int32_t block_size,
                            int32_t cap, void *d_out_u16, void *hip_stream);
 
+/* The census transform alone (stateless, asynchronous on hip_stream): d_img uint8 H x W with row stride
+ * stride_bytes (any pitch and alignment) -> d_out_u64 contiguous uint64 H x W codes of the window named by
+ * `cost` (DSX_COST_CENSUS9X7: 62 bits, DSX_COST_CENSUS5X5: 24 bits; the upper bits 0). */
+int dsx_census_device(const void *d_img, int32_t H, int32_t W, int64_t stride_bytes, int32_t cost, void *d_out_u64,
+                      void *hip_stream);
+
 /* Synchronous host-buffer compute (replaces matcher.compute, stereo_core.py:231).
  * L, R: uint8 H x W with row stride `stride_bytes` (>= W).  out_fixed: int16 H x W
  * (required, contiguous).  out_float: float32 H x W or NULL. */
@@ -201,7 +222,7 @@ int dsx_compute_host(dsx_handle *h, const uint8_t *L, const uint8_t *R, int32_t 
  * d_out_float (float32) are contiguous H x W device buffers; either may be NULL but not
  * both.  No host synchronisation, no allocation when the size matches the cached one.
  * Calls on different streams through ONE handle are safe: a configuration that uses the handle's
- * scratch (LR check, volume path, BT cost, SGM, sgbm_post, a prefilter's filtered images) orders a call
+ * scratch (LR check, volume path, BT or census cost, SGM, sgbm_post, a prefilter's filtered images) orders a call
  * on a new stream after the previous call's last kernel (stream wait on an event, no host wait); the
  * plain fused pass without a prefilter owns no scratch and runs concurrently.  Inputs and outputs
  * are the caller's: they must stay valid and unmodified until the work on hip_stream has completed. */
@@ -430,7 +451,7 @@ int dsx_kernel_times(dsx_handle *h, char *names, int names_cap, float *ms, int *
 int dsx_reset_times(dsx_handle *h);
 
 /* Device bytes currently held by the handle's buffer cache: the host-call staging images and
- * outputs, the prefiltered images, the LR keys and left winners, the cost volume, the BT records,
+ * outputs, the prefiltered images, the LR keys and left winners, the cost volume, the BT records, the census codes,
  * the SGM sums of either form, the sgbm_post input and workspace, and dsx_process_pair_device's maps and workspace.
  * Buffers kept from an earlier parameter set count until a shape or geometry change frees them. */
 int dsx_workspace_bytes(dsx_handle *h, int64_t *bytes);

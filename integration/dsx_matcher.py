@@ -28,6 +28,9 @@ class _Prefilter(ctypes.Structure):
 # preFilterType names -> DSX_PREFILTER_* (this build's own arithmetic, see include/dsx.h)
 PREFILTERS = {None: 0, "none": 0, "xsobel": 1, "mean": 2}
 
+# cost names -> DSX_COST_* (the census costs are this build's addition: Hamming distance of 9x7 / 5x5 codes)
+COSTS = {"sad": 0, "ssd": 1, "bt": 2, "census9x7": 3, "census5x5": 4}
+
 # sgbm_mode names (stereo_core.py:55-61) -> DSX_AGG_* (semi-global aggregation over SAD costs)
 SGBM_MODES = {"sgbm_3way": 3, "hh4": 4, "sgbm": 5, "hh": 8}
 
@@ -46,7 +49,8 @@ _lib.dsx_set_prefilter.argtypes = [_vp, ctypes.POINTER(_Prefilter)]
 def make_params(minDisparity=0, numDisparities=128, blockSize=5, disp12MaxDiff=1, uniquenessRatio=10,
                 cost=0, sgbm_mode=None, P1=0, P2=0, preFilterCap=31):
     # cost: 0 SAD, 1 SSD, 2 BT (OpenCV SGBM's Birchfield-Tomasi pixel cost on the preFilterCap-clipped
-    # x-derivative plus intensity)
+    # x-derivative plus intensity), 3 / 4 census 9x7 / 5x5 - or a name of COSTS
+    cost = COSTS[cost] if isinstance(cost, str) else cost
     p = _Params()
     _lib.dsx_default_params(ctypes.byref(p))
     p.min_disp, p.num_disp, p.block_size = minDisparity, numDisparities, blockSize

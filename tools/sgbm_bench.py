@@ -1,5 +1,5 @@
 """Timings of the OpenCV-SGBM-shaped modes next to plain block matching (device-resident inputs,
-stream events): 'bt' cost, + SGM (sgbm_3way / hh), + the sgbm_post tail, and the per-kernel split
+stream events): 'bt' cost, the census costs, + SGM (sgbm_3way / hh), + the sgbm_post tail, and the per-kernel split
 (HIP-event kernel timings of the handle).  Dev tool; one JSON line per (config, mode)."""
 import argparse
 import json
@@ -21,6 +21,12 @@ MODES = {
     "bt_sgm3_post": dict(cost="bt", aggregation="sgbm_3way", sgbm_post=True),
     "bt_hh_post": dict(cost="bt", aggregation="hh", sgbm_post=True),
     "sad_sgm3": dict(cost="sad", aggregation="sgbm_3way"),
+    # census costs: the block cost alone (the config's block), and the usual pairing - the per-pixel
+    # Hamming cost (block 1) under SGM with P1 8, P2 32
+    "census": dict(cost="census9x7", path="volume"),
+    "census_sgm3": dict(cost="census9x7", aggregation="sgbm_3way", block_size=1, p1=8, p2=32),
+    "census5_sgm3": dict(cost="census5x5", aggregation="sgbm_3way", block_size=1, p1=8, p2=32),
+    "census_hh": dict(cost="census9x7", aggregation="hh", block_size=1, p1=8, p2=32),
 }
 
 
@@ -67,7 +73,8 @@ def main():
             kt = {k: round(v[0], 4) for k, v in mt.kernel_times().items()}
             mt.close()
             print(json.dumps({"config": c, "mode": name, "H": H, "W": W, "D": D, "block": bs, "ms": round(ms, 4),
-                              "Mpix_s": round(H * W / ms / 1e3, 1), "kernels_ms": kt}), flush=True)
+                              "Mpix_s": round(H * W / ms / 1e3, 1), "kernels_ms": kt,
+                              "block_run": kw["block_size"]}), flush=True)
 
 
 if __name__ == "__main__":

@@ -53,6 +53,11 @@ DEF3(k_pk_mad_u16, "v_pk_mad_u16")
 DEF3(k_mad_u32_u24, "v_mad_u32_u24")
 DEF3(k_msad_u8, "v_msad_u8")
 DEF3(k_sad_hi_u8, "v_sad_hi_u8")
+// the census costs' instructions (dsx_census.hip): popcount + accumulate, xor, shift-add, funnel shift
+DEF2(k_bcnt_u32_b32, "v_bcnt_u32_b32")
+DEF2(k_xor_b32, "v_xor_b32")
+DEF3(k_lshl_add_u32, "v_lshl_add_u32")
+DEF3(k_alignbit_b32, "v_alignbit_b32")
 
 // 64-bit accumulator forms: INS d[2], s0[2], s1, d[2] (quad SAD) or d[2], s0[2], s1[2] (packed f32)
 #define DEFQ(NAME, INS, TAIL)                                                                      \
@@ -102,7 +107,8 @@ int main() {
     {"v_fma_f32", k_fma_f32}, {"v_sad_u8", k_sad_u8}, {"v_add3_u32", k_add3_u32}, {"v_min3_u32", k_min3_u32},
     {"v_perm_b32", k_perm_b32}, {"v_pk_mad_u16", k_pk_mad_u16}, {"v_mad_u32_u24", k_mad_u32_u24},
     {"v_msad_u8", k_msad_u8}, {"v_sad_hi_u8", k_sad_hi_u8}, {"v_qsad_pk_u16_u8", k_qsad}, {"v_mqsad_pk_u16_u8", k_mqsad},
-    {"v_pk_add_f32", k_pk_add_f32}, {"v_pk_mul_f32", k_pk_mul_f32}};
+    {"v_pk_add_f32", k_pk_add_f32}, {"v_pk_mul_f32", k_pk_mul_f32}, {"v_bcnt_u32_b32", k_bcnt_u32_b32},
+    {"v_xor_b32", k_xor_b32}, {"v_lshl_add_u32", k_lshl_add_u32}, {"v_alignbit_b32", k_alignbit_b32}};
   for (auto &x : ks) {
     const float ms = time_kernel(x.k, buf, blocks, threads);
     printf("%-16s %7.3f ms  %.2f cycles per wave-instr per SIMD (at 2.4 GHz)\n", x.n, ms, ms * 1e-3 * 2.4e9 * 1024 / wi);
