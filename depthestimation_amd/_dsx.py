@@ -42,6 +42,8 @@ EXPORTS = (
     "dsx_postprocess_device", "dsx_resize_area_table", "dsx_resize_area_device",
     "dsx_default_prefilter", "dsx_check_prefilter", "dsx_set_prefilter", "dsx_prefilter_device",
     "dsx_texture_sum_device", "dsx_census_device",
+    "dsx_default_refine", "dsx_check_refine", "dsx_wmedian_weights", "dsx_wmedian_device",
+    "dsx_postprocess_refine_device", "dsx_process_pair_refine_device",
 )
 
 
@@ -84,6 +86,20 @@ class DsxPrefilter(ctypes.Structure):
         ("size", ctypes.c_int32),
         ("cap", ctypes.c_int32),
         ("texture_threshold", ctypes.c_int32),
+        ("reserved", ctypes.c_int32 * 4),
+    ]
+
+
+REFINE = {"none": 0, "wmedian": 1}  # DSX_REFINE_* (include/dsx.h)
+
+
+class DsxRefine(ctypes.Structure):
+    """dsx_refine (include/dsx.h): the image-guided weighted median of the post-processing chain."""
+    _fields_ = [
+        ("type", ctypes.c_int32),
+        ("radius", ctypes.c_int32),
+        ("sigma", ctypes.c_int32),
+        ("fill", ctypes.c_int32),
         ("reserved", ctypes.c_int32 * 4),
     ]
 
@@ -135,7 +151,16 @@ def _bind(lib):
     vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
     P = ctypes.POINTER(DsxParams)
     F = ctypes.POINTER(DsxPrefilter)
+    RF = ctypes.POINTER(DsxRefine)
+    PP = ctypes.POINTER(DsxPostParams)
     sig = {
+        "dsx_default_refine": (None, [RF]),
+        "dsx_check_refine": (ctypes.c_int, [RF]),
+        "dsx_wmedian_weights": (ctypes.c_int, [i32, ctypes.POINTER(ctypes.c_uint16)]),
+        "dsx_wmedian_device": (ctypes.c_int, [vp, i32, i32, i64, vp, i64, RF, vp, vp]),
+        "dsx_postprocess_refine_device": (ctypes.c_int, [vp, i32, i32, i64, i32, PP, vp, vp, vp, ctypes.c_size_t, vp,
+                                                          RF, vp, i64]),
+        "dsx_process_pair_refine_device": (ctypes.c_int, [vp, vp, vp, i32, i32, i64, PP, vp, vp, vp, RF]),
         "dsx_default_prefilter": (None, [F]),
         "dsx_check_prefilter": (ctypes.c_int, [P, F]),
         "dsx_set_prefilter": (ctypes.c_int, [vp, F]),
@@ -294,6 +319,24 @@ def make_prefilter(prefilter_type="none", prefilter_size=9, prefilter_cap=31, te
     f.cap = int(prefilter_cap)
     f.texture_threshold = int(texture_threshold)
     return f
+
+
+def make_refine(refine="none", refine_radius=5, refine_sigma=8, refine_fill=True) -> DsxRefine:
+    """dsx_refine from the post-processing keywords; ValueError for an unknown name or a value out of range."""
+    rf = DsxRefine()
+    lib().dsx_default_refine(ctypes.byref(rf))
+    if refine is None:
+        refine = "none"
+    if refine not in REFINE:
+        raise ValueError(f"refine must be one of {list(REFINE)}, got {refine!r}")
+    rf.type = REFINE[refine]
+    if int(refine_sigma) != refine_sigma:
+        raise ValueError("refine_sigma must be an integer in [1, 64]")
+    rf.radius = int(refine_radius)
+    rf.sigma = int(refine_sigma)
+    rf.fill = int(bool(refine_fill))
+    check(lib().dsx_check_refine(ctypes.byref(rf)), "dsx_check_refine")
+    return rf
 
 
 def check_prefilter(p, f: DsxPrefilter) -> None:

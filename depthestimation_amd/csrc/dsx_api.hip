@@ -1166,13 +1166,42 @@ int dsx_postprocess_full_device(const void *d_disp, int32_t H, int32_t W, int64_
 }
 
 namespace {
+int check_refine(const dsx_refine *rf) {
+    if (!rf) return fail(DSX_EINVAL, "NULL refine");
+    if (rf->type == DSX_REFINE_NONE) return DSX_OK;
+    if (rf->type != DSX_REFINE_WMEDIAN) return fail(DSX_EINVAL, "refine type must be DSX_REFINE_NONE or DSX_REFINE_WMEDIAN");
+    if (rf->radius < dsx::kWmedianMinRadius || rf->radius > dsx::kWmedianMaxRadius)
+        return fail(DSX_EINVAL, "refine radius must be in [1, 7]");
+    if (rf->sigma < dsx::kWmedianMinSigma || rf->sigma > dsx::kWmedianMaxSigma)
+        return fail(DSX_EINVAL, "refine sigma must be in [1, 64]");
+    if (rf->fill != 0 && rf->fill != 1) return fail(DSX_EINVAL, "refine fill must be 0 or 1");
+    return DSX_OK;
+}
+
+// the chain's refinement hop from the C-ABI's arguments (rf NULL or type NONE: off, the guide unused)
+int refine_args(const dsx_refine *rf, const void *d_guide, int64_t guide_stride_bytes, int32_t W, dsx::RefineArgs &ra) {
+    ra = dsx::RefineArgs{};
+    if (!rf || rf->type == DSX_REFINE_NONE) return DSX_OK;
+    if (int rc = check_refine(rf)) return rc;
+    if (!d_guide) return fail(DSX_EINVAL, "refine needs a guide image (d_guide is NULL)");
+    if (guide_stride_bytes < W) return fail(DSX_EINVAL, "guide_stride_bytes must be >= W");
+    ra.type = dsx::kRefineWmedian;
+    ra.radius = rf->radius;
+    ra.sigma = rf->sigma;
+    ra.fill = rf->fill;
+    ra.guide = static_cast<const uint8_t *>(d_guide);
+    ra.guide_stride = guide_stride_bytes;
+    return DSX_OK;
+}
+
 // the stand-alone chain behind dsx_postprocess_full_ex_device and dsx_postprocess_device
 int post_full_standalone(const void *d_disp, int32_t H, int32_t W, int64_t in_pitch, int32_t crop,
                          int32_t max_speckle_size, double max_diff, int32_t apply_outlier_removal,
                          double outlier_threshold, int32_t outlier_kernel, int32_t fill_radius, int32_t fill_method,
                          const dsx::InpaintOpts &fill_opts, void *d_out_disp, void *d_out_depth, double focal_length,
                          double baseline, double doffs, double eps, double max_depth, int32_t has_max_depth,
-                         void *d_workspace, size_t workspace_bytes, void *hip_stream) {
+                         void *d_workspace, size_t workspace_bytes, void *hip_stream, const dsx_refine *rf = nullptr,
+                         const void *d_guide = nullptr, int64_t guide_stride_bytes = 0) {
     g_err.clear();
     if (fill_radius < 0) return fail(DSX_EINVAL, "fill_radius must be >= 0");
     if (fill_method != DSX_FILL_INPAINT && fill_method != DSX_FILL_NEAREST)
@@ -1182,6 +1211,8 @@ int post_full_standalone(const void *d_disp, int32_t H, int32_t W, int64_t in_pi
     if (!d_disp) return fail(DSX_EINVAL, "d_disp is NULL");
     if (H <= 0 || W <= 0 || in_pitch < W || crop < 0) return fail(DSX_EINVAL, "bad shape / pitch / crop");
     if (outlier_kernel < 1 || (outlier_kernel & 1) == 0) return fail(DSX_EINVAL, "outlier_kernel must be odd");
+    dsx::RefineArgs ra{};
+    if (int rc = refine_args(rf, d_guide, guide_stride_bytes, W, ra)) return rc;
     if (crop >= W || (!d_out_disp && !d_out_depth)) return DSX_OK;
     if (!d_workspace || workspace_bytes < dsx::post_full_workspace(H, W, crop))
         return fail(DSX_EINVAL, "workspace too small (dsx_postprocess_workspace_bytes)");
@@ -1212,7 +1243,7 @@ int post_full_standalone(const void *d_disp, int32_t H, int32_t W, int64_t in_pi
     a.fill_radius = fill_radius;
     a.fill_method = fill_method;
     a.fill_opts = fill_opts;
-    DSX_HIP(dsx::launch_post_full(a, d_workspace, static_cast<hipStream_t>(hip_stream)));
+    DSX_HIP(dsx::launch_post_full(a, d_workspace, static_cast<hipStream_t>(hip_stream), nullptr, &ra));
     return DSX_OK;
 }
 }  // namespace
@@ -1232,6 +1263,14 @@ int dsx_postprocess_full_ex_device(const void *d_disp, int32_t H, int32_t W, int
 int dsx_postprocess_device(const void *d_disp, int32_t H, int32_t W, int64_t in_pitch, int32_t crop,
                            const dsx_post_params *pp, void *d_out_disp, void *d_out_depth, void *d_workspace,
                            size_t workspace_bytes, void *hip_stream) {
+    return dsx_postprocess_refine_device(d_disp, H, W, in_pitch, crop, pp, d_out_disp, d_out_depth, d_workspace,
+                                         workspace_bytes, hip_stream, nullptr, nullptr, 0);
+}
+
+int dsx_postprocess_refine_device(const void *d_disp, int32_t H, int32_t W, int64_t in_pitch, int32_t crop,
+                                  const dsx_post_params *pp, void *d_out_disp, void *d_out_depth, void *d_workspace,
+                                  size_t workspace_bytes, void *hip_stream, const dsx_refine *rf, const void *d_guide,
+                                  int64_t guide_stride_bytes) {
     g_err.clear();
     if (!pp) return fail(DSX_EINVAL, "NULL post parameters");
     if (pp->mode != DSX_POST_FULL) return fail(DSX_EINVAL, "dsx_postprocess_device runs mode DSX_POST_FULL");
@@ -1242,7 +1281,44 @@ int dsx_postprocess_device(const void *d_disp, int32_t H, int32_t W, int64_t in_
                                 pp->apply_outlier_removal, pp->outlier_threshold, pp->outlier_kernel, pp->fill_radius,
                                 pp->fill_method, fo, d_out_disp, pp->has_depth ? d_out_depth : nullptr,
                                 pp->focal_length, pp->baseline, pp->doffs, pp->eps, pp->max_depth, pp->has_max_depth,
-                                d_workspace, workspace_bytes, hip_stream);
+                                d_workspace, workspace_bytes, hip_stream, rf, d_guide, guide_stride_bytes);
+}
+
+void dsx_default_refine(dsx_refine *rf) {
+    if (!rf) return;
+    std::memset(rf, 0, sizeof(*rf));
+    rf->type = DSX_REFINE_NONE;
+    rf->radius = 5;
+    rf->sigma = 8;
+    rf->fill = 1;
+}
+
+int dsx_check_refine(const dsx_refine *rf) {
+    g_err.clear();
+    return check_refine(rf);
+}
+
+int dsx_wmedian_weights(int32_t sigma, uint16_t *out256) {
+    g_err.clear();
+    if (sigma < dsx::kWmedianMinSigma || sigma > dsx::kWmedianMaxSigma) return fail(DSX_EINVAL, "sigma must be in [1, 64]");
+    if (!out256) return fail(DSX_EINVAL, "out256 is NULL");
+    return dsx::wmedian_weights(sigma, out256) == 0 ? DSX_OK : fail(DSX_EINVAL, "bad sigma");
+}
+
+int dsx_wmedian_device(const void *d_disp, int32_t H, int32_t W, int64_t in_pitch, const void *d_guide,
+                       int64_t guide_stride_bytes, const dsx_refine *rf, void *d_out, void *hip_stream) {
+    g_err.clear();
+    if (!d_disp || !d_out) return fail(DSX_EINVAL, "NULL input or output");
+    if (!d_guide) return fail(DSX_EINVAL, "d_guide is NULL");
+    if (d_out == d_disp) return fail(DSX_EINVAL, "d_out must not be d_disp (every window reads its neighbours' inputs)");
+    if (H <= 0 || W <= 0 || in_pitch < W || guide_stride_bytes < W) return fail(DSX_EINVAL, "bad shape / pitch / stride");
+    if ((int64_t)H > 16 * 65535) return fail(DSX_EINVAL, "image too tall (H > 1048560)");
+    if (int rc = check_refine(rf)) return rc;
+    if (rf->type != DSX_REFINE_WMEDIAN) return fail(DSX_EINVAL, "dsx_wmedian_device runs type DSX_REFINE_WMEDIAN");
+    DSX_HIP(dsx::launch_wmedian(static_cast<const float *>(d_disp), in_pitch, H, W, static_cast<const uint8_t *>(d_guide),
+                                guide_stride_bytes, rf->radius, rf->sigma, rf->fill, static_cast<float *>(d_out),
+                                static_cast<hipStream_t>(hip_stream)));
+    return DSX_OK;
 }
 
 size_t dsx_fill_nearest_workspace_bytes(int32_t H, int32_t W) {
@@ -1473,6 +1549,12 @@ int dsx_fill_holes_status_handle(dsx_handle *h) {
 
 int dsx_process_pair_device(dsx_handle *h, const void *dL, const void *dR, int32_t H, int32_t W, int64_t stride_bytes,
                             const dsx_post_params *pp, void *d_out_disp, void *d_out_depth, void *hip_stream) {
+    return dsx_process_pair_refine_device(h, dL, dR, H, W, stride_bytes, pp, d_out_disp, d_out_depth, hip_stream, nullptr);
+}
+
+int dsx_process_pair_refine_device(dsx_handle *h, const void *dL, const void *dR, int32_t H, int32_t W,
+                                   int64_t stride_bytes, const dsx_post_params *pp, void *d_out_disp, void *d_out_depth,
+                                   void *hip_stream, const dsx_refine *rf) {
     g_err.clear();
     if (!h || !pp) return fail(DSX_EINVAL, "NULL handle or post parameters");
     if (!dL || !dR) return fail(DSX_EINVAL, "input pointers are NULL");
@@ -1490,6 +1572,10 @@ int dsx_process_pair_device(dsx_handle *h, const void *dL, const void *dR, int32
     }
     if (h->p.float_mode != DSX_FLOAT_FIXED)
         return fail(DSX_EINVAL, "process_pair needs float_mode DSX_FLOAT_FIXED (stereo_core.py:232: fixed / 16)");
+    // the guide is the caller's raw left image (the chain reads it from column num_disp on), never the
+    // prefiltered copy; fast mode runs no refinement
+    dsx::RefineArgs ra{};
+    if (pp->mode == DSX_POST_FULL && (rc = refine_args(rf, dL, stride_bytes, W, ra))) return rc;
     const int crop = std::max(0, h->p.num_disp);  // stereo_core.py:168 crops num_disp columns
     const int Wc = W - crop;
     const bool depth = pp->has_depth != 0;
@@ -1568,7 +1654,7 @@ int dsx_process_pair_device(dsx_handle *h, const void *dL, const void *dR, int32
         a.fill_opts.spin_limit = pp->fill_spin_limit;
         a.fill_opts.steps = pp->fill_steps == 0 ? -1 : std::max(0, (int)pp->fill_steps);
         TimingHook hook(h);
-        hipError_t e = dsx::launch_post_full(a, h->ppWs, st, h->p.timing ? &hook : nullptr);
+        hipError_t e = dsx::launch_post_full(a, h->ppWs, st, h->p.timing ? &hook : nullptr, &ra);
         if (e != hipSuccess) return fail(DSX_EHIP, std::string("post-processing launch: ") + hipGetErrorString(e));
         if (hook.rc) return hook.rc;
     } else {

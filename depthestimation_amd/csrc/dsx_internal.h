@@ -199,7 +199,16 @@ struct LaunchHook {
 size_t sgbm_post_workspace(int H, int W);
 hipError_t launch_sgbm_post(const int16_t *in, int H, int W, int newv, int max_speckle, int max_diff16, int16_t *out16,
                             float *outf, void *ws, hipStream_t st);
-hipError_t launch_post_full(PostFullArgs a, void *ws, hipStream_t st, LaunchHook *hook = nullptr);
+// The image-guided refinement hop of the chain (dsx_refine of dsx.h): between the hole filling and the
+// median, on the cropped map.  guide: the uncropped H x W left image (read from column crop on).
+struct RefineArgs {
+    int type;  // kRefineNone | kRefineWmedian
+    int radius, sigma, fill;
+    const uint8_t *guide;
+    int64_t guide_stride;
+};
+hipError_t launch_post_full(PostFullArgs a, void *ws, hipStream_t st, LaunchHook *hook = nullptr,
+                            const RefineArgs *refine = nullptr);
 // true when launch_post_full runs the two-launch speckle form (else the four-launch union-find)
 bool post_full_two_launch(const PostFullArgs &a);
 
@@ -233,6 +242,18 @@ size_t nearest_workspace(int H, int W);  // the stepwise path's second buffer (k
 // path: kNearestFused (k <= kNearestFusedMaxK, ws unused) or kNearestStep (ws needed for k >= 2)
 hipError_t launch_nearest(const float *in, int64_t pitch, int H, int W, int k, float *out, float *ws, int path,
                           hipStream_t st);
+
+// Image-guided weighted median (dsx_wmedian.hip): out(p) = the weighted median of the valid (0 < d < inf)
+// taps of p's (2 r + 1)^2 window, weights T[|G(p) - G(q)|] from the guide.  Stateless, one launch.
+constexpr int kRefineNone = 0, kRefineWmedian = 1;  // DSX_REFINE_*
+constexpr int kWmedianMinRadius = 1, kWmedianMaxRadius = 7;
+constexpr int kWmedianMinSigma = 1, kWmedianMaxSigma = 64;
+// T[k] = max(1, floor(256 exp(-k / sigma) + 0.5)) in doubles; -1 for sigma outside [1, 64] or a null array.
+// Host only: the one C home of the weight rule.
+int wmedian_weights(int sigma, uint16_t *out256);
+// in: H x W floats, row pitch `pitch` elements; guide: H x W bytes, row stride gstride; out: contiguous, not in
+hipError_t launch_wmedian(const float *in, int64_t pitch, int H, int W, const uint8_t *guide, int64_t gstride, int r,
+                          int sigma, int fill, float *out, hipStream_t st);
 
 // Birchfield-Tomasi block costs into K1's volume layout (dsx_bt.hip, oracle/bt_cost.py)
 struct BtArgs {

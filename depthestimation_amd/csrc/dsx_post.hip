@@ -1046,7 +1046,7 @@ size_t post_full_workspace(int H, int W, int crop) {
            inpaint_workspace(H, Wc);
 }
 
-hipError_t launch_post_full(PostFullArgs a, void *ws, hipStream_t st, LaunchHook *hook) {
+hipError_t launch_post_full(PostFullArgs a, void *ws, hipStream_t st, LaunchHook *hook, const RefineArgs *refine) {
     const int Wc = a.W - a.crop;
     const size_t n = (size_t)a.H * Wc;
     const auto r = [](size_t b) { return (b + 255) & ~(size_t)255; };
@@ -1072,6 +1072,8 @@ hipError_t launch_post_full(PostFullArgs a, void *ws, hipStream_t st, LaunchHook
     };
     const int grid = (int)std::min<size_t>((n + 255) / 256, 4096);
     const bool fill = a.fill_radius > 0;
+    const bool refines = refine && refine->type == kRefineWmedian;
+    const bool hop = fill || refines;  // a stage between the outlier removal and the median
     if (post_full_two_launch(a)) {
         const dim3 g1((Wc + kSpTX - 1) / kSpTX, (a.H + kSpTY - 1) / kSpTY);
         const dim3 g2((Wc + kT3X - 1) / kT3X, (a.H + kT3Y - 1) / kT3Y);
@@ -1087,7 +1089,7 @@ hipError_t launch_post_full(PostFullArgs a, void *ws, hipStream_t st, LaunchHook
         hipLaunchKernelGGL(spk_tile, g1, dim3(256), 0, st, a);
         hipError_t e = done();
         if (e != hipSuccess) return e;
-        a.tail_t1 = fill ? 1 : 0;
+        a.tail_t1 = hop ? 1 : 0;
         mark("post_tail");
         const size_t dyn = (size_t)4 * (a.max_speckle + 1) * sizeof(int);
         const int rr = a.kernel / 2;
@@ -1107,7 +1109,7 @@ hipError_t launch_post_full(PostFullArgs a, void *ws, hipStream_t st, LaunchHook
             }
             (void)hipFree(a.tl_tile);
         }
-        if (e != hipSuccess || !fill) return e;
+        if (e != hipSuccess || !hop) return e;
     } else {
         mark("speckle_legacy");
         const int ntx = (Wc + kCcTX - 1) / kCcTX, nty = (a.H + kCcTY - 1) / kCcTY;
@@ -1121,12 +1123,12 @@ hipError_t launch_post_full(PostFullArgs a, void *ws, hipStream_t st, LaunchHook
         hipError_t e = done();
         if (e != hipSuccess) return e;
         if (a.kernel / 2 <= kTailR) {
-            a.tail_t1 = fill ? 1 : 0;
+            a.tail_t1 = hop ? 1 : 0;
             mark("post_tail");
             hipLaunchKernelGGL(post_tail, dim3((Wc + kTailTX - 1) / kTailTX, (a.H + kTailTY - 1) / kTailTY),
                                dim3(kTailTX * kTailTY), 0, st, a);
             e = done();
-            if (e != hipSuccess || !fill) return e;
+            if (e != hipSuccess || !hop) return e;
         }
     }
     const float *med_in = a.t0;
@@ -1158,6 +1160,16 @@ hipError_t launch_post_full(PostFullArgs a, void *ws, hipStream_t st, LaunchHook
             if (!fo.status_key) fo.status_key = ws;
             e = launch_inpaint(med_in, Wc, a.H, Wc, a.fill_radius, dst, inpaint_ws, st, fo);
         }
+        if (hook) hook->after(st);
+        if (e != hipSuccess) return e;
+        med_in = dst;
+    }
+    if (refines) {
+        // the guided weighted median on the cleaned (and filled) map: one more hop of the t0 / t1 pair
+        float *dst = med_in == a.t0 ? a.t1 : a.t0;
+        mark("refine_wmedian");
+        hipError_t e = launch_wmedian(med_in, Wc, a.H, Wc, refine->guide + a.crop, refine->guide_stride, refine->radius,
+                                      refine->sigma, refine->fill, dst, st);
         if (hook) hook->after(st);
         if (e != hipSuccess) return e;
         med_in = dst;

@@ -298,15 +298,22 @@ class HipBlockMatcher:
     def process_pair_device(self, left, right, fast_mode=False, max_speckle_size=100, max_diff=1.0,
                             apply_outlier_removal=True, outlier_threshold=2.5, outlier_kernel=5, fill_radius=0,
                             focal_length=None, baseline=None, doffs=0.0, eps=1e-6, max_depth=None, out_disp=None,
-                            out_depth=None, stream=None, fill_spin_limit=0, fill_steps=0, fill_method="inpaint"):
+                            out_depth=None, stream=None, fill_spin_limit=0, fill_steps=0, fill_method="inpaint",
+                            refine="none", refine_radius=5, refine_sigma=8, refine_fill=True):
         """StereoCore._process_pair (stereo_core.py:162-200) in ONE C-ABI call
         (dsx_process_pair_device): matcher -> crop [:, num_disp:] -> fast-mode median or
         postprocess_disparity (speckles, outliers, hole filling when ``fill_radius`` > 0: Telea with
         ``fill_method`` 'inpaint', the iterated dilation with 'nearest', where ``fill_radius`` is the
         kernel_size; median) -> depth when focal length and baseline are given.  ``left``/``right``: uint8 HIP
         tensors H x W (unit column stride, equal row strides).  Returns float32 HIP tensors
-        (disparity H x (W - num_disp), depth or None); asynchronous on ``stream``."""
+        (disparity H x (W - num_disp), depth or None); asynchronous on ``stream``.
+
+        ``refine`` 'wmedian' (dsx_process_pair_refine_device) runs the image-guided weighted median
+        (postprocess.weighted_median_filter; ``refine_radius`` 1..7, ``refine_sigma`` 1..64, ``refine_fill``)
+        after the hole filling and before the median, guided by the raw ``left`` from column num_disp on;
+        fast mode ignores it.  Per call, like every other post parameter."""
         import torch
+        rf = _dsx.make_refine(refine, refine_radius, refine_sigma, refine_fill)
         if left.dtype != right.dtype or left.shape != right.shape or left.dim() != 2:
             raise ValueError("left and right must be uint8 H x W tensors of the same shape")
         if str(left.dtype) != "torch.uint8" or left.stride(1) != 1 or right.stride(1) != 1 or \
@@ -342,6 +349,13 @@ class HipBlockMatcher:
         pp.fill_steps = int(fill_steps)
         pp.fill_method = _fill_method(fill_method)
         sptr = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
+        if rf.type:
+            rc = _dsx.lib().dsx_process_pair_refine_device(self._handle(), left.data_ptr(), right.data_ptr(), H, W,
+                                                           left.stride(0), ctypes.byref(pp), _ptr(out_disp),
+                                                           _ptr(out_depth) if want_depth else None, sptr,
+                                                           ctypes.byref(rf))
+            _dsx.check(rc, "dsx_process_pair_refine_device")
+            return out_disp, (out_depth if want_depth else None)
         rc = _dsx.lib().dsx_process_pair_device(self._handle(), left.data_ptr(), right.data_ptr(), H, W,
                                                 left.stride(0), ctypes.byref(pp), _ptr(out_disp),
                                                 _ptr(out_depth) if want_depth else None, sptr)
@@ -531,17 +545,29 @@ def _keep_until_done(t, stream):
 def postprocess_full_device(disp, crop, max_speckle_size=50, max_diff=1.0, apply_outlier_removal=True,
                             outlier_threshold=3.0, outlier_kernel=5, focal_length=None, baseline=None, doffs=0.0,
                             eps=1e-6, max_depth=None, stream=None, apply_hole_filling=False, fill_kernel=3,
-                            workspace=None, fill_method="inpaint"):
+                            workspace=None, fill_method="inpaint", guide=None, refine="none", refine_radius=5,
+                            refine_sigma=8, refine_fill=True):
     """postprocess_disparity (postprocess.py:120-171) + depth on the device
     (dsx_postprocess_device): speckles -> outliers -> hole filling when
     ``apply_hole_filling`` (``fill_method`` 'inpaint': Telea with radius ``fill_kernel``; 'nearest':
     ``fill_kernel`` masked dilations, stateless) -> 3x3 median -> depth, all enqueued on ``stream``
     without host synchronisation.  ``disp``: float32 H x W HIP tensor.
     Returns (disp_cropped, depth or None) as HIP tensors.  ``workspace``: a ``FillWorkspace`` (default:
-    one per device and stream), whose flag ``fill_holes_status(workspace)`` reports a timed-out fill."""
+    one per device and stream), whose flag ``fill_holes_status(workspace)`` reports a timed-out fill.
+
+    ``refine`` 'wmedian' (dsx_postprocess_refine_device): the image-guided weighted median between the hole
+    filling and the median, with ``guide`` the UNCROPPED uint8 H x W left image on ``disp``'s device (unit
+    column stride; read from column ``crop`` on)."""
     import torch
 
     method = _fill_method(fill_method)
+    rf = _dsx.make_refine(refine, refine_radius, refine_sigma, refine_fill)
+    if rf.type:
+        if guide is None:
+            raise ValueError("refine needs guide (the uncropped left image on the device)")
+        if guide.dtype != torch.uint8 or guide.dim() != 2 or guide.stride(1) != 1 or guide.device != disp.device \
+                or guide.shape != disp.shape:
+            raise ValueError("guide must be a uint8 device tensor of disp's shape with unit column stride")
     if disp.dtype != torch.float32 or disp.dim() != 2 or disp.stride(1) != 1 or not disp.is_cuda:
         raise ValueError("disp must be a float32 H x W device tensor with unit column stride")
     H, W = disp.shape
@@ -572,12 +598,49 @@ def postprocess_full_device(disp, crop, max_speckle_size=50, max_diff=1.0, apply
     pp.eps = float(eps)
     pp.max_depth = float(max_depth or 0.0)
     pp.has_max_depth = int(max_depth is not None)
-    rc = L.dsx_postprocess_device(disp.data_ptr(), H, W, disp.stride(0), int(crop), ctypes.byref(pp),
-                                  out_disp.data_ptr(), out_depth.data_ptr() if want_depth else None, ws.data_ptr(),
-                                  nbytes, sptr)
-    _dsx.check(rc, "dsx_postprocess_device")
+    if rf.type:
+        rc = L.dsx_postprocess_refine_device(disp.data_ptr(), H, W, disp.stride(0), int(crop), ctypes.byref(pp),
+                                             out_disp.data_ptr(), out_depth.data_ptr() if want_depth else None,
+                                             ws.data_ptr(), nbytes, sptr, ctypes.byref(rf), guide.data_ptr(),
+                                             guide.stride(0))
+        _dsx.check(rc, "dsx_postprocess_refine_device")
+    else:
+        rc = L.dsx_postprocess_device(disp.data_ptr(), H, W, disp.stride(0), int(crop), ctypes.byref(pp),
+                                      out_disp.data_ptr(), out_depth.data_ptr() if want_depth else None,
+                                      ws.data_ptr(), nbytes, sptr)
+        _dsx.check(rc, "dsx_postprocess_device")
     _keep_until_done(ws, stream)
     return out_disp, out_depth
+
+
+def wmedian_device(disp, guide, radius=5, sigma=8, fill=True, out=None, stream=None):
+    """The image-guided weighted median alone on the device (dsx_wmedian_device; host restatement
+    postprocess.weighted_median_filter, equal bit for bit).  ``disp``: float32 H x W HIP tensor, ``guide``:
+    uint8 H x W HIP tensor (both unit column stride, any row stride or offset); ``out`` must not be
+    ``disp``.  Stateless, asynchronous on ``stream``; returns the contiguous float32 H x W result."""
+    import torch
+
+    if disp.dtype != torch.float32 or disp.dim() != 2 or disp.stride(1) != 1 or not disp.is_cuda:
+        raise ValueError("disp must be a float32 H x W device tensor with unit column stride")
+    if guide is None:
+        raise ValueError("guide is required (a uint8 H x W device tensor)")
+    if guide.dtype != torch.uint8 or guide.shape != disp.shape or guide.device != disp.device or \
+            (guide.dim() == 2 and guide.shape[1] > 1 and guide.stride(1) != 1):
+        raise ValueError("guide must be a uint8 tensor of disp's shape on its device with unit column stride")
+    rf = _dsx.make_refine("wmedian", radius, sigma, fill)
+    H, W = disp.shape
+    if out is None:
+        out = torch.empty((H, W), dtype=torch.float32, device=disp.device)
+    elif out is disp or (hasattr(out, "data_ptr") and H and W and out.data_ptr() == disp.data_ptr()):
+        raise ValueError("out must not be disp (every window reads its neighbours' inputs)")
+    elif out.shape != (H, W) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != disp.device:
+        raise ValueError("out must be a contiguous float32 H x W tensor on the input's device")
+    if H == 0 or W == 0:
+        return out
+    rc = _dsx.lib().dsx_wmedian_device(disp.data_ptr(), H, W, max(disp.stride(0), W), guide.data_ptr(),
+                                       max(guide.stride(0), W), ctypes.byref(rf), out.data_ptr(), _stream_ptr(stream))
+    _dsx.check(rc, "dsx_wmedian_device")
+    return out
 
 
 def fill_holes_status(workspace=None):

@@ -15,6 +15,10 @@ each function restates the documented OpenCV semantics with numpy/scipy:
                           order (see _telea_inpaint); 'nearest': iterated elliptical dilation
                           (postprocess.py:106-116).
 * ``median_blur3``      - 3 x 3 median with BORDER_REPLICATE (cv2.medianBlur, ksize 3).
+* ``weighted_median_filter`` - this build's own refinement (nothing in the reference reads the
+                          ``left_image`` it passes): a weighted median of the map, weighted by intensity
+                          similarity in the left image, optionally filling invalid pixels (dsx_refine in
+                          include/dsx.h states the rule; csrc/dsx_wmedian.hip is the device form).
 
 Parity against OpenCV is unpinned (cv2 absent); the reference's own behavioural test
 (tests/test_postproc_logic.py:35-42: the post-processed map is smoother than the fast-mode
@@ -31,7 +35,7 @@ from scipy.sparse import coo_matrix
 from scipy.sparse.csgraph import connected_components
 
 __all__ = ["filter_speckles", "detect_outliers", "fill_holes", "postprocess_disparity", "median_blur3",
-           "filter_speckles_int16"]
+           "filter_speckles_int16", "wmedian_weights", "weighted_median_filter"]
 
 
 def filter_speckles_int16(img: np.ndarray, new_val: int, max_speckle_size: int, max_diff: int) -> np.ndarray:
@@ -488,8 +492,96 @@ def median_blur3(a) -> np.ndarray:
     return ndimage.median_filter(np.asarray(a, np.float32), size=3, mode="nearest")
 
 
+def wmedian_weights(sigma) -> np.ndarray:
+    """The weight table of the guided weighted median: T[k] = max(1, floor(256 exp(-k / sigma) + 0.5)) for
+    k = 0..255, uint16, in float64 (its C twin: dsx_wmedian_weights).  ``sigma``: an integer in 1..64."""
+    if int(sigma) != sigma or not 1 <= int(sigma) <= 64:
+        raise ValueError("sigma must be an integer in [1, 64]")
+    k = np.arange(256, dtype=np.float64)
+    return np.maximum(1.0, np.floor(256.0 * np.exp(-k / float(int(sigma))) + 0.5)).astype(np.uint16)
+
+
+_WM_CHUNK = 1 << 22  # window taps held at once by weighted_median_filter (rows are processed in strips)
+
+
+def weighted_median_filter(disparity, guide, radius=5, sigma=8, fill=True) -> np.ndarray:
+    """Image-guided weighted median (dsx_refine in include/dsx.h), the host restatement of
+    csrc/dsx_wmedian.hip, bit for bit.  ``disparity`` float32 H x W, ``guide`` uint8 H x W.
+
+    A value is valid iff 0 < d < +inf.  For pixel p the valid taps q of the window |i|, |j| <= radius
+    (taps outside the image skipped) weigh w_q = T[|G(p) - G(q)|] (``wmedian_weights``), S is their sum,
+    and out(p) is the smallest tap value v with 2 * sum(w_q : d_q <= v) >= S.  Where no tap is valid, or
+    d(p) is invalid and ``fill`` is off, out(p) = d(p) with its bits unchanged.  The output is always a bit
+    pattern of the window: values are selected, never computed."""
+    d = np.ascontiguousarray(disparity, dtype=np.float32)
+    g = np.asarray(guide)
+    if d.ndim != 2 or g.shape != d.shape or g.dtype != np.uint8:
+        raise ValueError("weighted_median_filter needs a float32 H x W map and a uint8 guide of the same shape")
+    r = int(radius)
+    if not 1 <= r <= 7:
+        raise ValueError("radius must be in [1, 7]")
+    T = wmedian_weights(sigma).astype(np.int64)
+    H, W = d.shape
+    out = d.copy()
+    if H == 0 or W == 0:
+        return out
+    n = 2 * r + 1
+    with np.errstate(invalid="ignore"):
+        valid = (d > 0) & (d < np.inf)
+    bits = d.view(np.uint32)
+    # valid values are positive finite floats: their bit patterns order as the values do
+    key = np.where(valid, bits, np.uint32(0xFFFFFFFF))
+    kp = np.pad(key, r, constant_values=np.uint32(0xFFFFFFFF))   # outside the image: no tap
+    gp = np.pad(g.astype(np.int64), r)
+    rows = max(1, _WM_CHUNK // (n * n * W))
+    for y0 in range(0, H, rows):
+        y1 = min(H, y0 + rows)
+        h = y1 - y0
+        ks = np.empty((n * n, h, W), np.uint32)
+        ws = np.empty((n * n, h, W), np.int64)
+        gc = gp[y0 + r:y1 + r, r:W + r]
+        t = 0
+        for dy in range(n):
+            for dx in range(n):
+                k = kp[y0 + dy:y1 + dy, dx:dx + W]
+                ks[t] = k
+                ws[t] = np.where(k != np.uint32(0xFFFFFFFF), T[np.abs(gc - gp[y0 + dy:y1 + dy, dx:dx + W])], 0)
+                t += 1
+        order = np.argsort(ks, axis=0, kind="stable")
+        ks = np.take_along_axis(ks, order, axis=0)
+        cum = np.cumsum(np.take_along_axis(ws, order, axis=0), axis=0)
+        S = cum[-1]
+        pick = np.argmax(2 * cum >= S[None], axis=0)  # first sorted tap whose running weight reaches half
+        sel = np.take_along_axis(ks, pick[None], axis=0)[0]
+        take = S > 0
+        if not fill:
+            take &= valid[y0:y1]
+        o = out[y0:y1].view(np.uint32)
+        o[take] = sel[take]
+    return out
+
+
+_REFINE_NAMES = ("none", "wmedian")
+
+
 def postprocess_disparity(disparity, **kwargs):
-    """postprocess.py:120-171: speckles -> outliers -> (holes) -> 3x3 median."""
+    """postprocess.py:120-171: speckles -> outliers -> (holes) -> (refine) -> 3x3 median.
+
+    ``refine='wmedian'`` (this build's addition; 'none' is the default) runs ``weighted_median_filter``
+    with ``left_image`` - the left rectified gray image over the same pixels as ``disparity`` - as the
+    guide and ``refine_radius`` (5), ``refine_sigma`` (8), ``refine_fill`` (True), after the hole filling,
+    if any, and before the median.  It raises ValueError without a ``left_image`` of the map's shape."""
+    refine = kwargs.get("refine", "none") or "none"
+    if refine not in _REFINE_NAMES:
+        raise ValueError(f"refine must be one of {list(_REFINE_NAMES)}, got {refine!r}")
+    if refine == "wmedian":
+        guide = kwargs.get("left_image")
+        if guide is None:
+            raise ValueError("refine='wmedian' needs left_image (the left rectified gray image) as its guide")
+        guide = np.asarray(guide)
+        if guide.dtype != np.uint8 or guide.shape != np.shape(disparity):
+            raise ValueError(f"refine='wmedian': left_image must be uint8 of the disparity's shape "
+                             f"{np.shape(disparity)}, got {guide.dtype} {guide.shape}")
     result = filter_speckles(np.array(disparity, np.float32, copy=True), kwargs.get("max_speckle_size", 50),
                              kwargs.get("max_diff", 1))
     if kwargs.get("apply_outlier_removal", True):
@@ -498,4 +590,7 @@ def postprocess_disparity(disparity, **kwargs):
         result[om] = 0
     if kwargs.get("apply_hole_filling", True):
         result = fill_holes(result, method=kwargs.get("fill_method", "inpaint"), kernel_size=kwargs.get("fill_kernel", 3))
+    if refine == "wmedian":
+        result = weighted_median_filter(result, guide, radius=kwargs.get("refine_radius", 5),
+                                        sigma=kwargs.get("refine_sigma", 8), fill=kwargs.get("refine_fill", True))
     return median_blur3(result)

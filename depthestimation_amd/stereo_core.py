@@ -42,6 +42,15 @@ Keys added to ``sgbm_params`` (accepted by ``configure_sgbm`` like the reference
                                        the cap, 'prefilter_size' (odd, 5..21) the window of 'mean')
   'texture_threshold': int            (0 = off; > 0 needs a prefilter: pixels whose filtered block sums
                                        less than this much |P - cap| become invalid)
+  'refine': 'none' | 'wmedian'         ('none', the default.  'wmedian': the image-guided weighted median of
+                                       postprocess.weighted_median_filter after the hole filling, if any,
+                                       and before the median, guided by the left rectified image - the
+                                       `left_image` the reference passes and never reads.  It thins the
+                                       fattened foreground at depth edges and, with 'refine_fill' (True),
+                                       fills invalid pixels from similar-looking neighbours: one stateless
+                                       launch, fast enough for video.  'refine_radius' 1..7 (5),
+                                       'refine_sigma' 1..64 grey levels (8).  Ignored in fast mode, as
+                                       'hole_filling' is)
 Keys of the reference that have no block-matching meaning are kept, validated and reported
 but do not change the result: 'prefilter_cap' unless 'cost' is 'bt' or a prefilter is set, 'speckle_window_size' /
 'speckle_range' unless 'sgbm_post' is set, and 'sgbm_mode' / P1 / P2 while 'aggregation' is 'none'
@@ -142,6 +151,10 @@ class StereoCore:
             'prefilter_type': 'none',
             'prefilter_size': 9,
             'texture_threshold': 0,
+            'refine': 'none',
+            'refine_radius': 5,
+            'refine_sigma': 8,
+            'refine_fill': True,
         }
         self._build_sgbm()
         self.disparity_map = None
@@ -156,6 +169,13 @@ class StereoCore:
             raise ValueError("Invalid parameter value for 'aggregation': expected 'none' or 'sgm'")
         if p.get('fill_method', 'inpaint') not in ('inpaint', 'nearest'):
             raise ValueError("Invalid parameter value for 'fill_method': expected 'inpaint' or 'nearest'")
+        if p.get('refine', 'none') not in ('none', 'wmedian'):
+            raise ValueError("Invalid parameter value for 'refine': expected 'none' or 'wmedian'")
+        r, sg = p.get('refine_radius', 5), p.get('refine_sigma', 8)
+        if isinstance(r, bool) or int(r) != r or not 1 <= int(r) <= 7:
+            raise ValueError("Invalid parameter value for 'refine_radius': expected an integer in [1, 7]")
+        if isinstance(sg, bool) or int(sg) != sg or not 1 <= int(sg) <= 64:
+            raise ValueError("Invalid parameter value for 'refine_sigma': expected an integer in [1, 64]")
         self.P1 = 8 * p['block_size'] ** 2
         self.P2 = 32 * p['block_size'] ** 2
         self.mode = p.get('sgbm_mode', 'sgbm_3way') if p.get('sgbm_mode') in _SGBM_MODES else 'sgbm_3way'
@@ -200,6 +220,12 @@ class StereoCore:
         self.sgbm_params.update(kwargs)
         self._build_sgbm()
 
+    def _refine_kwargs(self) -> dict:
+        """The 'refine*' keys as the keywords of postprocess_disparity and the device calls."""
+        p = self.sgbm_params
+        return dict(refine=p.get('refine', 'none'), refine_radius=int(p.get('refine_radius', 5)),
+                    refine_sigma=int(p.get('refine_sigma', 8)), refine_fill=bool(p.get('refine_fill', True)))
+
     def get_sgbm_params(self) -> Dict[str, int]:
         return self.sgbm_params.copy()
 
@@ -224,6 +250,9 @@ class StereoCore:
         postprocess -> depth when focal length and baseline are set."""
         disparity_px = self.compute_disparity(left_img, right_img)
         disparity_px = disparity_px[:, self.sgbm_params['num_disp']:]
+        refine = self._refine_kwargs()
+        if refine['refine'] != 'none' and not self.fast_mode:
+            left_img = np.asarray(left_img)[:, self.sgbm_params['num_disp']:]  # the guide: the map's own pixels
         if self.fast_mode:
             disparity_px = median_blur3(disparity_px.astype(np.float32))
         else:
@@ -236,6 +265,7 @@ class StereoCore:
                 fill_method=self.sgbm_params.get('fill_method', 'inpaint'),
                 apply_outlier_removal=True,
                 apply_hole_filling=self.sgbm_params.get('hole_filling', False),
+                **refine,
             )
         f_pixels = self.sgbm_params.get('focal_length', None)
         baseline_m = self.sgbm_params.get('baseline', None)
@@ -311,7 +341,8 @@ class StereoCore:
         """Device-resident ``_process_pair`` (stereo_core.py:162-200) for rectified uint8 HIP
         tensors: matcher -> crop -> post-processing -> depth, all in HBM.  Fast mode: 3x3 median
         (SURVEY.md 8f row F1); otherwise speckle filter + outlier removal (+ hole filling
-        with ``hole_filling``, by ``fill_method``) + median (row F2).  Returns float32 HIP tensors
+        with ``hole_filling``, by ``fill_method``; + the guided weighted median with ``refine``, guided
+        by ``left``) + median (row F2).  Returns float32 HIP tensors
         (disparity_px, depth_m or None)."""
         p = self.sgbm_params
         f, B = p.get('focal_length'), p.get('baseline')
@@ -329,7 +360,7 @@ class StereoCore:
                 left, right, fast_mode=self.fast_mode, max_speckle_size=int(100 * self.downscale_factor),
                 max_diff=1.0, apply_outlier_removal=True, outlier_threshold=2.5, outlier_kernel=5,
                 fill_radius=3 if p.get('hole_filling', False) else 0, focal_length=f, baseline=B, doffs=doffs,
-                eps=eps, max_depth=max_depth, stream=stream, fill_method=method)
+                eps=eps, max_depth=max_depth, stream=stream, fill_method=method, **self._refine_kwargs())
         disp = self.compute_disparity_device(left, right, stream=stream)
         self._fill_check = None
         if self.fast_mode:
@@ -343,7 +374,7 @@ class StereoCore:
                                        outlier_kernel=5, focal_length=f, baseline=B, doffs=doffs, eps=eps,
                                        max_depth=max_depth, stream=stream,
                                        apply_hole_filling=bool(p.get('hole_filling', False)), fill_kernel=3,
-                                       fill_method=method)
+                                       fill_method=method, guide=left, **self._refine_kwargs())
 
     def disparity_to_depth(self, disp: np.ndarray, f_pixels: float, baseline_m: float, doffs: float = 0.0,
                            eps: float = 1e-6, max_depth: Optional[float] = None) -> np.ndarray:

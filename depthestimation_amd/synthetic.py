@@ -69,3 +69,41 @@ def striped_pair(H: int, W: int, min_disp: int = 0, num_disp: int = 64, seed: in
 
 def _threshold(img: np.ndarray) -> np.ndarray:
     return np.where(img > 127, 255, 0).astype(np.uint8)
+
+
+def layered_pair(H: int, W: int, num_disp: int = 32, seed: int = 1234, disparities=(6, 12, 7, 13, 8),
+                 levels=(60, 200, 100, 240, 140), amplitude: int = 8):
+    """An occlusion-correct layered scene: returns (L, R, d_gt), d_gt float32 H x W.
+
+    The columns from ``num_disp`` on (what survives the drop-in crop) are split into len(disparities)
+    vertical layers of equal width; layer i has the constant integer disparity ``disparities[i]`` and grey
+    level ``levels[i]`` + a uniform texture in [-amplitude, amplitude]; the first layer also covers the
+    columns left of ``num_disp``.  The right view is rendered far to near - every layer is shifted left by
+    its disparity and nearer layers overwrite farther ones - so a foreground edge hides background in one
+    view only, as a real scene does; right pixels that no layer reaches take their own texture around the
+    mean level.  Depth edges coincide with grey-level edges: what an image-guided filter can use.  Keep the
+    disparity jumps smaller than the radius of a filter that is to reach across the occlusion band."""
+    if len(disparities) != len(levels) or not disparities:
+        raise ValueError("disparities and levels must be non-empty sequences of equal length")
+    if min(disparities) < 0 or max(disparities) >= max(int(num_disp), 1):
+        raise ValueError("disparities must lie in [0, num_disp)")
+    rng = np.random.default_rng(seed)
+    n = len(disparities)
+    a = int(amplitude)
+    edges = (min(int(num_disp), W) + np.linspace(0, max(W - int(num_disp), 0), n + 1)).astype(int)
+    edges[0] = 0
+    edges[-1] = W
+    L = np.zeros((H, W), np.int32)
+    d_gt = np.zeros((H, W), np.float32)
+    for i in range(n):
+        x0, x1 = edges[i], edges[i + 1]
+        L[:, x0:x1] = int(levels[i]) + rng.integers(-a, a + 1, (H, x1 - x0))
+        d_gt[:, x0:x1] = float(disparities[i])
+    L = np.clip(L, 0, 255).astype(np.uint8)
+    R = np.clip(int(np.mean(levels)) + rng.integers(-a, a + 1, (H, W)), 0, 255).astype(np.uint8)
+    for i in np.argsort(np.asarray(disparities), kind="stable"):  # far (small disparity) first
+        x0, x1, d = edges[i], edges[i + 1], int(disparities[i])
+        lo = max(x0, d)  # left columns whose right position x - d is inside the image
+        if x1 > lo:
+            R[:, lo - d:x1 - d] = L[:, lo:x1]
+    return L, R, d_gt

@@ -32,7 +32,10 @@
 extern "C" {
 #endif
 
-#define DSX_VERSION 106 /* additive since 1.0.6 (layouts unchanged): DSX_COST_CENSUS*, dsx_census_device, dsx_resize_area_*, dsx_fill_nearest_*,
+#define DSX_VERSION 106 /* additive since 1.0.6 (layouts unchanged): dsx_refine, dsx_default_refine, dsx_check_refine,
+                           dsx_wmedian_weights, dsx_wmedian_device, dsx_postprocess_refine_device,
+                           dsx_process_pair_refine_device (image-guided weighted median);
+                           DSX_COST_CENSUS*, dsx_census_device, dsx_resize_area_*, dsx_fill_nearest_*,
                            dsx_postprocess_device,
                            dsx_prefilter, dsx_default_prefilter, dsx_check_prefilter, dsx_set_prefilter,
                            dsx_prefilter_device, dsx_texture_sum_device (matcher prefilter + texture threshold);
@@ -406,6 +409,65 @@ int dsx_process_pair_device(dsx_handle *h, const void *dL, const void *dR, int32
 int dsx_postprocess_device(const void *d_disp, int32_t H, int32_t W, int64_t in_pitch, int32_t crop,
                            const dsx_post_params *pp, void *d_out_disp, void *d_out_depth, void *d_workspace,
                            size_t workspace_bytes, void *hip_stream);
+
+/* Image-guided refinement of the disparity map: a weighted median whose weights come from the intensity
+ * similarity in the left rectified image, with optional filling of invalid pixels from their similar-looking
+ * neighbours.  An addition of this build (as the prefilter and the census costs are): parity with nothing
+ * outside this repository is claimed.  It gives the `left_image` that StereoCore._process_pair hands to
+ * postprocess_disparity (stereo_core.py:175-184) a meaning.  With d the float32 H x W map, G the uint8 H x W
+ * guide over the same pixels, r = radius, s = sigma:
+ *   validity   a value is valid iff 0 < d < +inf (NaN, +-0, negatives and +inf are invalid);
+ *   weights    T[k] = max(1, floor(256 exp(-k / s) + 0.5)), k = 0..255, in doubles on the host
+ *              (dsx_wmedian_weights; the device never computes it);
+ *   window     |i|, |j| <= r around p, taps outside the image skipped; N = its valid taps q (p included if
+ *              valid), w_q = T[|G(p) - G(q)|], S = the sum of the w_q (<= 225 * 256);
+ *   output     N empty, or d(p) invalid and fill == 0: out(p) = d(p), the input bits unchanged;
+ *              otherwise the smallest v among the d_q with 2 * (sum of w_q over d_q <= v) >= S.
+ * The output is always a bit pattern of the window: no arithmetic touches a disparity, so the device equals
+ * the host restatement (depthestimation_amd/postprocess.py weighted_median_filter) bit for bit.  One
+ * stateless launch: no workspace, no grid barrier, no status flag, nothing to time out.
+ * In the chain (mode DSX_POST_FULL) it runs after the hole filling, if any, and before the 3x3 median; with
+ * fill = 1 and hole filling off it is the hole filler.  DSX_POST_FAST ignores it, as it ignores hole filling. */
+#define DSX_REFINE_NONE 0
+#define DSX_REFINE_WMEDIAN 1
+typedef struct dsx_refine {
+    int32_t type;   /* DSX_REFINE_*                                            */
+    int32_t radius; /* 1..7                                                    */
+    int32_t sigma;  /* 1..64, in grey levels                                   */
+    int32_t fill;   /* 0 | 1: invalid pixels take the median of their window   */
+    int32_t reserved[4];
+} dsx_refine;
+
+/* none, radius 5, sigma 8, fill 1 */
+void dsx_default_refine(dsx_refine *rf);
+
+/* Validate a refinement (host only, no device).  Type NONE passes whatever the other fields hold. */
+int dsx_check_refine(const dsx_refine *rf);
+
+/* T for sigma in 1..64 into out256[0..255] (host only). */
+int dsx_wmedian_weights(int32_t sigma, uint16_t *out256);
+
+/* The filter alone.  d_disp: float32 H x W, row pitch `in_pitch` elements (any alignment; rows that are 16-byte
+ * aligned take 16-byte loads); d_guide: uint8 H x W, row stride guide_stride_bytes (any alignment); rf: type
+ * DSX_REFINE_WMEDIAN; d_out: contiguous float32 H x W, not d_disp.  H <= 1048560.  Stateless, asynchronous
+ * on hip_stream; argument errors are reported before any HIP call. */
+int dsx_wmedian_device(const void *d_disp, int32_t H, int32_t W, int64_t in_pitch, const void *d_guide,
+                       int64_t guide_stride_bytes, const dsx_refine *rf, void *d_out, void *hip_stream);
+
+/* dsx_postprocess_device with the refinement between the hole filling and the median.  d_guide: the
+ * UNCROPPED uint8 H x W left image, row stride guide_stride_bytes; the chain reads it from column `crop` on.
+ * rf NULL or type NONE: exactly dsx_postprocess_device (d_guide may be NULL).  No extra workspace. */
+int dsx_postprocess_refine_device(const void *d_disp, int32_t H, int32_t W, int64_t in_pitch, int32_t crop,
+                                  const dsx_post_params *pp, void *d_out_disp, void *d_out_depth, void *d_workspace,
+                                  size_t workspace_bytes, void *hip_stream, const dsx_refine *rf, const void *d_guide,
+                                  int64_t guide_stride_bytes);
+
+/* dsx_process_pair_device with the refinement.  The guide is the caller's dL from column num_disp on: the raw
+ * image, also when the handle has a prefilter set.  rf NULL or type NONE: exactly dsx_process_pair_device.
+ * Reported under the name refine_wmedian by dsx_kernel_times. */
+int dsx_process_pair_refine_device(dsx_handle *h, const void *dL, const void *dR, int32_t H, int32_t W,
+                                   int64_t stride_bytes, const dsx_post_params *pp, void *d_out_disp,
+                                   void *d_out_depth, void *hip_stream, const dsx_refine *rf);
 
 /* Per-frame rectification on the device, replacing cv2.cvtColor(BGR2GRAY)
  * + cv2.remap(INTER_LINEAR) of rectify.py:183-186 (cached-maps path) and stereo_core.py:155-159:

@@ -7,6 +7,7 @@ Reports per config: host wall ms per frame (back to back, one sync at the end), 
 (stream events around the loop) and the handle's per-kernel HIP-event breakdown.
 
 usage: python tools/dropin_bench.py [--configs c2r c4] [--frames 200] [--hole-filling inpaint|nearest]
+                                    [--refine wmedian --refine-radius R --refine-sigma S]
 """
 import argparse
 import json
@@ -32,6 +33,10 @@ def main():
                     help="the round-3 four-launch speckle union-find (DSX_POST_LEGACY) for a before/after")
     ap.add_argument("--hole-filling", choices=["inpaint", "nearest"], default=None,
                     help="run with hole_filling=True and this fill_method (default: hole filling off)")
+    ap.add_argument("--refine", choices=["none", "wmedian"], default="none",
+                    help="the image-guided weighted median between the hole filling and the median")
+    ap.add_argument("--refine-radius", type=int, default=5)
+    ap.add_argument("--refine-sigma", type=int, default=8)
     args = ap.parse_args()
     if args.legacy_post:
         os.environ["DSX_POST_LEGACY"] = "1"
@@ -47,6 +52,8 @@ def main():
         core.configure_sgbm(num_disp=D, block_size=cfg["block_size"], focal_length=700.0, baseline=0.1)
         if args.hole_filling:
             core.configure_sgbm(hole_filling=True, fill_method=args.hole_filling)
+        if args.refine != "none":
+            core.configure_sgbm(refine=args.refine, refine_radius=args.refine_radius, refine_sigma=args.refine_sigma)
         stream = torch.cuda.current_stream(dev)
         for i in range(20):
             core.estimate_depth_device(*frames[i % 4])
@@ -65,7 +72,9 @@ def main():
                 "disp12_max_diff": core.sgbm_params["disp12_max_diff"], "fast_mode": core.fast_mode,
                 "wall_ms_per_frame": round(wall, 4), "gpu_ms_per_frame": round(gpu, 4),
                 "mpix_s_wall": round(H * W / wall / 1e3, 1), "legacy_post": bool(args.legacy_post),
-                "hole_filling": args.hole_filling}
+                "hole_filling": args.hole_filling, "refine": args.refine}
+        if args.refine != "none":
+            line.update(refine_radius=args.refine_radius, refine_sigma=args.refine_sigma)
         # per-kernel breakdown: the same pipeline through a matcher with HIP-event timing
         core.sgbm = HipBlockMatcher(**dict(core.sgbm.params, timing=True))
         for i in range(10):
