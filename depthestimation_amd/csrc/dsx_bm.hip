@@ -74,6 +74,24 @@ constexpr int kWpeSsd = 4;  // SSD blocks of >= 4 waves
 #ifndef DSX_ROWSTEP_SARGS
 #define DSX_ROWSTEP_SARGS DSX_ROWSTEP_SREF
 #endif
+// The rotated loop holds row y - 1's two output stores behind step y's last chunk, and the staging of step y + 1's
+// rows behind the box phase then waits with vmcnt(1) / (0) behind them: vmcnt counts loads and stores in order, so
+// each step drained its stores.  Two orders avoid that, each on its own switch (profiles/stageahead_ab.txt):
+// -DDSX_ROWSTEP_STORELATE=0 restores the stores behind the last chunk.  With it (STL in bm2_segment, default) the tail
+// forms the two outputs where it did and issues the stores at the end of the step, behind the staging; the loads
+// keep the whole step to land.  C2 with three frames in flight 47,214 -> 47,567 Mpix/s (+0.7 %, every run above
+// every parent run).
+// -DDSX_ROWSTEP_STAGEAHEAD=1 switches ON the staging directly behind the last chunk, in front of the stores (STA),
+// which is off by default: the loads then have only the column update to land, SQ_WAIT_ANY per C2 launch rose
+// 16.12 M -> 16.54 M and the step ran 1.0 % slower than the parent's (46,884 against 47,342 Mpix/s).
+#ifndef DSX_ROWSTEP_STAGEAHEAD
+#define DSX_ROWSTEP_STAGEAHEAD 0
+#endif
+constexpr bool kRowstepStageahead = DSX_ROWSTEP_STAGEAHEAD;  // the loops that run OVL
+#ifndef DSX_ROWSTEP_STORELATE
+#define DSX_ROWSTEP_STORELATE 1
+#endif
+constexpr bool kRowstepStorelate = DSX_ROWSTEP_STORELATE;  // the loops that run OVL
 constexpr bool kRowstepSref = DSX_ROWSTEP_SREF;          // pair layout, one-wave left pass, R <= 4
 constexpr bool kRowstepSargs = DSX_ROWSTEP_SARGS;        // the same loops: launch arguments re-read behind the last chunk
 constexpr bool kRowstepOverlap = DSX_ROWSTEP_OVERLAP;    // pair layout, one-wave left pass, R <= 5
@@ -112,6 +130,15 @@ constexpr bool kRowstepKey2 = DSX_ROWSTEP_KEY2;
 #ifndef DSX_SEGSTART_SPART
 #define DSX_SEGSTART_SPART 0
 #endif
+// -DDSX_SEGSTART_ROW0=1 switches ON the first step's two prefetch loads in front of the init SAD loop (SR0 in
+// bm2_segment): the batched-init builds of the merged staging hold the two dwords across that loop, and step yb, whose
+// body is only the box phase, issues no prefetch of its own; its rows are staged in front of the row loop.  Off by
+// default: alone it ran C2 0.5 % below the parent (47,117 against 47,342 Mpix/s, spreads 0.2 - 0.5 %), next to
+// STAGEAHEAD 0.4 % above it, next to STORELATE 2.1 % below it.
+#ifndef DSX_SEGSTART_ROW0
+#define DSX_SEGSTART_ROW0 0
+#endif
+constexpr bool kSegstartRow0 = DSX_SEGSTART_ROW0;
 constexpr bool kSegstartAhead = DSX_SEGSTART_AHEAD;
 constexpr bool kSegstartBatch = DSX_SEGSTART_BATCH;
 constexpr bool kSegstartSpart = DSX_SEGSTART_SPART;
@@ -400,6 +427,13 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
             *reinterpret_cast<uint4 *>(sp) = make_uint4(__builtin_amdgcn_perm(0u, w, m_sel0), __builtin_amdgcn_perm(0u, w, m_sel1),
                                                         __builtin_amdgcn_perm(0u, w, m_sel2), __builtin_amdgcn_perm(0u, w, m_sel3));
     };
+    // SR0 (the builds that batch their init rows, IBT below, and stage merged rows): step yb's prefetch - rows
+    // yb + 1 + R and yb - R, the one an init row again - issued once the init batch is in LDS, in front of the init SAD
+    // loop, and held in sr_n / sr_o across it.  Issued at the top of step yb, whose body is only the box phase, the
+    // staging of that step waits for a whole global round trip.  Only the loads move: the init's LDS rows overlap the
+    // slots, so the stores to the slots stay behind the barrier that ends the init.
+    constexpr bool SR0 = kSegstartRow0 && kSegstartBatch && MRG && R <= 4 && (SIDE == 0 || SIDE == 4);
+    uint32_t sr_n = 0, sr_o = 0;
     auto ld = [&](int r, uint32_t &w0, uint32_t &w1, uint32_t &w2, uint32_t &w3, uint32_t &rf) __attribute__((always_inline)) {
         const int yy = clampi2(r, 0, H - 1);
         // The row base is wave-uniform and the lane's part a small non-negative offset (FAST:
@@ -698,6 +732,12 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
             }
         }
         block_sync<NW>();
+        if constexpr (SR0) {
+            static_assert(!SR0 || IBT, "the first step's rows ride behind the batched init loads");
+            ldm(yb + 1 + R, sr_n);
+            ldm(yb - R, sr_o);
+            __builtin_amdgcn_sched_barrier(0);
+        }
         // this lane's pair entry for column c: TP_g[d0 + NC - 1 - c] (8-B aligned); groups in a
         // runtime loop, columns unrolled (a full unroll of both hoists every LDS read and spills)
         const uint8_t *tb = smem + d0 * 8;
@@ -881,6 +921,19 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
     // 8-column chunk does.
     constexpr bool CUQ = !SSD && SIDE == 0 && NW == 1 && R < 6 && kRowstepKey2 && !PTAIL;
     constexpr bool OVL = kRowstepOverlap && CUQ, AHD = kRowstepAhead && CUQ;
+    // STA (the loops that run OVL): rotated, the step holds row y - 1's two output stores behind its last chunk, so
+    // staging behind the box phase waits with vmcnt(1) / vmcnt(0) behind them - vmcnt counts loads and stores in
+    // order, so that is a store round trip per step.  The staging of step y + 1's rows therefore stands directly
+    // behind the last chunk, in front of the stages that store: slots par ^ 2 and (par ^ 2) + 1 were last read by
+    // step y - 1's column update, and a one-wave block's LDS operations execute in order.  A segment's first step
+    // has no column update and no store in front of its staging, which stays behind the box phase.
+    constexpr bool STA = kRowstepStageahead && OVL;
+    // STL (the same loops): the loads keep the whole step to land - the staging stays behind the box phase - and the
+    // two output stores of row y - 1 follow it: the outputs (the x16 value, the parabola float) are held across the
+    // box phase in e_fx / e_pf, and the next wait that counts the stores is the next step's staging, a step later.
+    constexpr bool STL = kRowstepStorelate && OVL;
+    int e_fx = 0;
+    float e_pf = 0.0f;
     constexpr int CQ = 4, NQ = (NC + CQ - 1) / CQ;
     // SREF (the unaligned-dword copy of these loops): the reference row is wave-uniform, so the column update takes
     // it from SGPRs - v_sad_u8 / v_sad_hi_u8 are VOP3 and read the reference byte as their one scalar operand -
@@ -930,9 +983,19 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
     };
     // rl / er: the sub-pixel and output stages read their launch arguments from er (SRA: the row loop's re-read ones
     // behind its last chunk) instead of the segment's
-    auto estage = [&](auto sc, int ey, auto rl, const Bm2Args &er) __attribute__((always_inline)) {
+    // the two output stores of a row, apart from the stage that forms the outputs where that stage defers them (STL)
+    auto estore = [&](int ey, const Bm2Args &ea) __attribute__((always_inline)) {
+        if (eh == 0 && ex < W) {
+            const long o = fout + (long)ey * W + ex;
+            if (ea.out_fixed) ea.out_fixed[o] = (int16_t)e_fx;
+            if (ea.out_float) ea.out_float[o] = ea.float_mode == 0 ? (float)(int16_t)e_fx * 0.0625f : e_pf;
+        }
+    };
+    // dfr: the output stage leaves its stores to estore
+    auto estage = [&](auto sc, int ey, auto rl, const Bm2Args &er, auto dfr) __attribute__((always_inline)) {
         constexpr int s = decltype(sc)::value;
         constexpr bool RL = decltype(rl)::value;
+        constexpr bool DFR = decltype(dfr)::value;
         auto pick = [&]() __attribute__((always_inline)) -> const Bm2Args & {
             if constexpr (RL) return er;
             else return a;
@@ -1005,7 +1068,14 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
                 const uint32_t real_max = padv_e < (1u << 24) ? padv_e : (1u << 24);
                 if (nm < real_max && nm * (uint32_t)(100 - ea.uniq) < ecb * 100u) valid = false;
             }
-            if (eh == 0 && ex < W) {
+            if constexpr (DFR) {
+                e_fx = valid ? (int16_t)(m * 16 + ef) : (int16_t)((m - 1) * 16);
+                if (eh == 0 && ex < W && ea.out_float && ea.float_mode != 0) {
+                    float pf = (float)(m + eb);
+                    if (esp) pf = (float)(m + eb) + (float)((int32_t)ecm - (int32_t)ecp) / (float)(2 * eden);
+                    e_pf = valid ? pf : (float)(m - 1);
+                }
+            } else if (eh == 0 && ex < W) {
                 const long o = fout + (long)ey * W + ex;
                 const int16_t fx = valid ? (int16_t)(m * 16 + ef) : (int16_t)((m - 1) * 16);
                 if (ea.out_fixed) ea.out_fixed[o] = fx;
@@ -1024,6 +1094,13 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
     if constexpr (SREF) {  // the rows of the segment's first column update (step yb + 1)
         sld(yb + 1 + R, qn, shn);
         sld(yb - R, qo, sho);
+    }
+    if constexpr (SR0) {  // step yb's staging: the init's rows are consumed (the barrier that ends the init) and the loads old
+        if (yb + 1 < ye) {
+            stm(smem + stg, sr_n);
+            stm(smem + stg + SLOT, sr_o);
+        }
+        stg = (2 * m_lane + (uint32_t)(2 * SLOT)) - stg;
     }
     for (int y = yb; y < ye; ++y) {
         const Bm2Args &a = kargs_row<SIDE == 3>(a_in);
@@ -1062,7 +1139,12 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
         // are dead.  First form (!RL2): under `if (more)`; writing the zeros then waits for the
         // previous step's loads and stores (s_waitcnt vmcnt(0) at the loop header).
         uint32_t pn0 = 0, pn1 = 0, pn2 = 0, pn3 = 0, pnr = 0, po0 = 0, po1 = 0, po2 = 0, po3 = 0, por = 0;
-        if constexpr (MRG) {
+        if constexpr (SR0) {  // step yb's rows were loaded in front of the init SAD loop and staged in front of this loop
+            if (y > yb) {
+                ldm(y + 1 + R, pn0);
+                ldm(y - R, po0);
+            }
+        } else if constexpr (MRG) {
             ldm(y + 1 + R, pn0);
             ldm(y - R, po0);
         } else if (RL2 || more) {
@@ -1154,7 +1236,7 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
                 constexpr int q = decltype(qc)::value;
                 if constexpr (q < NQ) {
                     __builtin_amdgcn_sched_barrier(0);
-                    if constexpr (OVL && q < NRS + 3) estage(qc, y - 1, std::false_type{}, a);
+                    if constexpr (OVL && q < NRS + 3) estage(qc, y - 1, std::false_type{}, a, std::false_type{});
                     if constexpr (!AHD) rd(qc);
                     else if constexpr (q + 1 < NQ) rd(std::integral_constant<int, q + 1>{});
                     __builtin_amdgcn_sched_barrier(0);
@@ -1170,6 +1252,22 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
             chunk(std::integral_constant<int, 10>{}); chunk(std::integral_constant<int, 11>{});
             static_assert(NQ <= 12 && NQ >= 7, "chunks of the overlapped column update");
             __builtin_amdgcn_sched_barrier(0);
+            if constexpr (STA) {  // step y + 1's rows to their slots, in front of the tail's stores
+                if constexpr (MRG) {
+                    if (more) {
+                        stm(smem + stg, pn0);
+                        stm(smem + stg + SLOT, po0);
+                    }
+                    stg = (2 * m_lane + (uint32_t)(2 * SLOT)) - stg;
+                } else {
+                    if (more) {
+                        st_at(smem + stg, pn0, pn1, pn2, pn3, pnr);
+                        st_at(smem + stg + SLOT, po0, po1, po2, po3, por);
+                    }
+                    stg = (uint32_t)(32 * tid + 2 * SLOT) - stg;
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
             if constexpr (SREF) {  // step y + 1's rows (clamped like the prefetch: the segment's last step reads a row nobody uses)
                 sld(y + 1 + R, qn, shn);
                 sld(y - R, qo, sho);
@@ -1179,8 +1277,8 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
             const Bm2Args &ea = kargs_row<SRA>(a);
             if constexpr (SRA) __builtin_amdgcn_sched_barrier(0);
             if constexpr (OVL) {
-                if constexpr (NQ < NRS + 3) estage(std::integral_constant<int, NRS + 2>{}, y - 1, std::integral_constant<bool, SRA>{}, ea);
-                estage(std::integral_constant<int, NRS + 3>{}, y - 1, std::integral_constant<bool, SRA>{}, ea);
+                if constexpr (NQ < NRS + 3) estage(std::integral_constant<int, NRS + 2>{}, y - 1, std::integral_constant<bool, SRA>{}, ea, std::false_type{});
+                estage(std::integral_constant<int, NRS + 3>{}, y - 1, std::integral_constant<bool, SRA>{}, ea, std::integral_constant<bool, STL>{});
             }
           }
         } else if (y > yb) {
@@ -1410,25 +1508,34 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
         // block has passed the mid-step barrier above since then, and the barrier that ends the
         // step orders these writes before step y + 1 reads them (the end barrier of step y - 1 alone
         // already separates them from their last readers).  The epilogue reads the tile only.
+        // That holds for the sequential loops.  Rotated (OVL), the step's stores are those of row y - 1's tail and
+        // stand behind the last chunk, in front of this place: the waits below drain them again unless the staging
+        // moves in front of them (STA) or they move behind it (STL).
         if constexpr (RL2) {
             // the lane's staging address alternates between slots 0 and 2: carried across the steps and
             // flipped with one subtraction (rebuilt from par, it came out as one v_mad per store)
+            // STA: only the segment's first step stages here (the others did behind their last chunk); SR0: every
+            // step but the first, whose rows were staged in front of the loop
+            [[maybe_unused]] const bool late = STA ? (!SR0 && y == yb) : (!SR0 || y > yb);
             if constexpr (MRG) {
-                if (more) {
+                if (more && late) {
                     stm(smem + stg, pn0);
                     stm(smem + stg + SLOT, po0);
                 }
-                stg = (2 * m_lane + (uint32_t)(2 * SLOT)) - stg;
+                if (late) stg = (2 * m_lane + (uint32_t)(2 * SLOT)) - stg;
             } else if constexpr (SIDE != 3) {
-                if (more) {
+                if (more && late) {
                     st_at(smem + stg, pn0, pn1, pn2, pn3, pnr);
                     st_at(smem + stg + SLOT, po0, po1, po2, po3, por);
                 }
-                stg = (uint32_t)(32 * tid + 2 * SLOT) - stg;
+                if (late) stg = (uint32_t)(32 * tid + 2 * SLOT) - stg;
             } else if (more) {  // LR pass, at its register budget: no carried address (R = 1 spilled 16 B more)
                 st(par ^ 2, pn0, pn1, pn2, pn3, pnr);
                 st((par ^ 2) + 1, po0, po1, po2, po3, por);
             }
+        }
+        if constexpr (STL) {  // row y - 1's outputs, formed behind the last chunk
+            if (y > yb) estore(y - 1, a);
         }
         DSX_STAMP(5);
         if constexpr (side == 2) {
@@ -1702,7 +1809,7 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
     }
     if constexpr (OVL) {  // the segment's last row: nothing is kept across segments
         auto dr = [&](auto sc) __attribute__((always_inline)) {
-            if constexpr (decltype(sc)::value <= NRS + 3) estage(sc, ye - 1, std::false_type{}, a);
+            if constexpr (decltype(sc)::value <= NRS + 3) estage(sc, ye - 1, std::false_type{}, a, std::false_type{});
         };
         dr(std::integral_constant<int, 0>{}); dr(std::integral_constant<int, 1>{}); dr(std::integral_constant<int, 2>{});
         dr(std::integral_constant<int, 3>{}); dr(std::integral_constant<int, 4>{}); dr(std::integral_constant<int, 5>{});
@@ -1940,8 +2047,13 @@ static hipError_t launch_bm2_side(const Bm2Args &a, hipStream_t st) {
         const char *e = getenv("DSX_FLIGHT_GRID");
         return !(e && *e == '0');
     }();
+    // The plain left pass of the pair layout (SIDE 0, C2's kernel) takes half of the residency: with the output stores
+    // behind the staging its optimum moved (grids of 1, 2/3, 1/2: 46.5k / 47.7k / 48.1k Mpix/s, three runs each within
+    // 0.1k; profiles/stageahead_ab.txt).  The LR passes lose at half (C4 above), and the SAD1 layout, which gained there
+    // in this sweep (C1 38.8k -> 39.8k), once fell to 24.8k on one of two runs at half and stays on two thirds.
     if (flight_grid && a.in_flight && NW == 1 && blocks_per_cu[dev] >= 3) {
-        const long g23 = (long)num_cu[dev] * (blocks_per_cu[dev] * 2 / 3);
+        const bool half = !SSD && SIDE == 0;
+        const long g23 = (long)num_cu[dev] * (half ? blocks_per_cu[dev] / 2 : blocks_per_cu[dev] * 2 / 3);
         if (g23 < grid) grid = g23;
     }
     if (a.grid_override > 0) grid = a.grid_override;

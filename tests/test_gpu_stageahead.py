@@ -1,0 +1,359 @@
+"""Row staging and output stores of the rotated row loop of the fused pass (csrc/dsx_bm.hip, bm2_segment).  Three
+forms reorder them, each behind its own switch:
+
+  -DDSX_ROWSTEP_STORELATE (default 1): row y - 1's two output stores, formed behind step y's last column chunk, are
+      issued at the end of step y, behind the staging of step y + 1's rows;
+  -DDSX_ROWSTEP_STAGEAHEAD (default 0): step y writes the rows of step y + 1 to their LDS slots directly behind its
+      last column chunk, in front of those stores; a segment's first step has no column update and keeps its staging
+      behind the box phase;
+  -DDSX_SEGSTART_ROW0 (default 0): a segment's first step's two rows are loaded in front of the init SAD loop and
+      staged in front of the row loop.
+
+The cases hold for every setting of the three.  They were run on the builds STORELATE / STAGEAHEAD / ROW0 = 1 0 0 (the
+default), 0 1 0, 0 0 1, 0 1 1 and 1 0 1.
+
+What these forms can get wrong is which slot pair a step writes (it alternates on y & 1 and the carried staging
+address flips in a new place), a slot written while its last reader still needs it, an output stored for the wrong
+row or held across a step that has none, and the places the staging stands in: a one-step segment stages nothing
+that is used, a two-step segment uses the early-staged slots exactly once, and from three steps on a step reads what
+the step before staged.  So the cases are chosen by segment length, first-row parity and position
+in the frame, from a restatement of the host partition (csrc/dsx_partition.h, equal block weights) and of the
+kernel's test for the unaligned-dword copy ("f:" below; the others, "c:", take clamped bytes), and every case asserts
+from that restatement that the classes it is there for occur.
+
+Every comparison is bit for bit over all pixels against the C oracle (oracle/cref.py): the int16 x16 map and the
+float map - float mode 'fixed' against x16 / 16 (exact in f32), 'parabola' by bit pattern.
+
+Base: D = 128, block 9, W = 256: the valid band starts at x = 127, strips 3..7 run, x0 = 160 and 192 on the
+unaligned-dword copy and 96, 128, 224 on the clamped one.  H is between 12 and 40.
+"""
+from __future__ import annotations
+
+import numpy as np
+import pytest
+
+from depthestimation_amd.synthetic import stereo_pair
+from oracle.cref import CRef
+
+pytestmark = pytest.mark.gpu
+
+M, D, BS, W0 = 0, 128, 9, 256
+BASE = dict(min_disp=M, num_disp=D, block_size=BS, cost="sad", disp12_max_diff=-1)
+
+
+@pytest.fixture(scope="module")
+def torch_dev():
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    return torch
+
+
+_CREF = []
+_WANT = {}
+
+
+def _want(key, L, R, m, d, bs, u, sp, lr=-1):
+    """Oracle maps, computed once per (input, parameters) and shared by the tests."""
+    k = (key, m, d, bs, u, sp, lr)
+    if k not in _WANT:
+        if not _CREF:
+            _CREF.append(CRef())
+        _WANT[k] = _CREF[0](L, R, m, d, bs, "sad", u, lr, sp)
+    return _WANT[k]
+
+
+# ---- host partition, restated (bm2_partition with one age level: every block weighs the same) --------
+
+def _partition(NG, S, sb, nf, H, XL, XU, TX=32, w8=11):
+    NS = S * nf
+    if NG < NS:
+        return [b * NS * H // NG for b in range(NG + 1)]
+    slo = min(max((XL + TX - 1) // TX - sb, 0), S)
+    shi = min(max(XU // TX - sb + 1, slo), S)
+    if w8 < 8 or NG * 8 < NS * w8 + 8 * NS:
+        w8 = 8
+    ex = w8 - 8
+    Pf = lambda s: 8 * s + ex * (min(s, slo) + max(0, s - shi))  # noqa: E731
+    Uf = Pf(S)
+    U = Uf * nf
+    P = lambda g: (g // S) * Uf + Pf(g % S)  # noqa: E731
+    start, b = [], 0
+    for g in range(NS + 1):
+        while b < NG and b * U < P(g) * NG:
+            b += 1
+        start.append(b)
+    part = [0] * (NG + 1)
+    for g in range(NS):
+        qd = start[g + 1] - start[g]
+        for bb in range(start[g], start[g + 1] + 1):
+            part[bb] = g * H + (bb - start[g]) * H // qd
+    part[NG] = NS * H
+    return part
+
+
+def _dp(d):
+    """Disparities per block: SAD1 (one per lane) up to 64, else pairs in one, two or four waves."""
+    return 64 if d <= 64 else (128 if d <= 128 else (256 if d <= 256 else 512))
+
+
+def _blocks(H, gb, W=W0, m=M, nf=1, R=BS // 2, d=D):
+    """Per block of a left-pass launch its segments (frame, strip, first row, row count, fast), in order."""
+    NC, Dp = 32 + 2 * R, _dp(d)
+    NJ4, NC4 = (NC + Dp + 3) // 4, (NC + 3) // 4
+    xlo, xhi = max(0, m + d - 1), min(W - 1, W - 1 + m)
+    sb = xlo // 32
+    S = xhi // 32 + 1 - sb
+    XL = max(4 * NJ4 + R + m - NC + 1, R)
+    XU = min(W - 1 + R + m - NC + 1, W - 1 + R - 4 * NC4 + 1)
+    T = S * nf * H
+    NG = min(gb, T) if gb > 0 else T  # the resident capacity (thousands of blocks) exceeds T at these sizes
+    part = _partition(NG, S, sb, nf, H, XL, XU)
+
+    def fast(s):  # bm2's test for the unaligned-dword copy, left pass
+        x0 = (sb + s) * 32
+        PB = x0 - R - m + NC - 1
+        return PB - 4 * NJ4 >= 0 and PB <= W - 1 and x0 - R >= 0 and x0 - R + 4 * NC4 - 1 <= W - 1
+
+    out = []
+    for b in range(NG):
+        it, lin1, segs = part[b], part[b + 1], []
+        while it < lin1:
+            sidx, yb = it // H, it % H
+            ye = min(H, yb + lin1 - it)
+            segs.append((sidx // S, sidx % S, yb, ye - yb, fast(sidx % S)))
+            it += ye - yb
+        out.append(segs)
+    assert sum(s[3] for segs in out for s in segs) == T
+    return out
+
+
+def _kinds(blocks, H):
+    """Segment classes of a launch; 'f:' marks the unaligned-dword copy, 'c:' the clamped one.
+
+    n1 / n2 / n3 / n4+: segments of one, two, three, four or more steps.  even / odd: parity of the first row of a
+    segment of two steps or more (one that reads a staged slot pair).  row0 / last: a segment of two steps or more that
+    starts at row 0 / ends at row H - 1.  next_strip: a block that goes from a strip's last row to the next strip's
+    row 0; frame_cut: a segment that ends a frame's last strip while the next block starts the next frame's first."""
+    k = set()
+    for b in blocks:
+        for s in b:
+            p = "f:" if s[4] else "c:"
+            n = s[3]
+            k.add(p + ("n4+" if n >= 4 else f"n{n}"))
+            if n >= 2:
+                k.add(p + ("odd" if s[2] & 1 else "even"))
+                if s[2] == 0:
+                    k.add(p + "row0")
+                if s[2] + n == H:
+                    k.add(p + "last")
+        for p, q in zip(b, b[1:]):
+            if p[0] == q[0] and q[1] == p[1] + 1 and p[2] + p[3] == H and q[2] == 0:
+                k.add("next_strip")
+    for b, c in zip(blocks, blocks[1:]):
+        if b and c and c[0][0] == b[-1][0] + 1 and c[0][1] == 0 and c[0][2] == 0 and b[-1][2] + b[-1][3] == H:
+            k.add("frame_cut")
+    return k
+
+
+# ---- comparison --------------------------------------------------------------------------------------
+
+def _check(got, want, what):
+    bad = np.argwhere(got != want)
+    assert bad.size == 0, (f"{what}: {len(bad)} of {got.size} pixels differ, first {bad[:4].tolist()}: "
+                           f"got {got[tuple(bad[0])]} want {want[tuple(bad[0])]}")
+
+
+def _check_maps(fixed, flt, want, what, fmode="fixed"):
+    wf = want["fixed"]
+    _check(fixed.cpu().numpy(), wf, what + " fixed")
+    if fmode == "fixed":
+        _check(flt.cpu().numpy(), wf.astype(np.float32) / np.float32(16), what + " float")
+    else:
+        _check(flt.cpu().numpy().view(np.int32), want["parabola"].view(np.int32), what + " float (parabola, bits)")
+
+
+def _run(torch, dL, dR, shape, want, what, grids, fmode="fixed", **kw):
+    from depthestimation_amd.matcher import HipBlockMatcher
+    for g in grids:
+        mt = HipBlockMatcher(grid_blocks=g, float_mode=fmode, **kw)
+        try:
+            fx = torch.empty(shape, dtype=torch.int16, device="cuda")
+            fl = torch.empty(shape, dtype=torch.float32, device="cuda")
+            mt.compute_device(dL, dR, out_fixed=fx, out_float=fl)
+            torch.cuda.synchronize()
+            _check_maps(fx, fl, want, f"{what} grid_blocks={g}", fmode)
+        finally:
+            mt.close()
+
+
+def _pair(H, W=W0, m=M, d=D, seed=0):
+    L, R, _ = stereo_pair(H, W, m, d, seed=9100 + 13 * H + seed)
+    return L, R
+
+
+def _both_modes(torch, key, L, R, grids, what, d=D, bs=BS, u=10, lr=-1, **kw):
+    """Both float modes (the int16 map with each)."""
+    want = _want(key, L, R, M, d, bs, u, True, lr)
+    dL, dR = torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda()
+    par = dict(BASE, num_disp=d, block_size=bs, uniqueness_ratio=u, disp12_max_diff=lr)
+    par.update(kw)
+    for fmode in ("fixed", "parabola"):
+        _run(torch, dL, dR, L.shape, want, f"{what} {fmode}", grids, fmode=fmode, **par)
+
+
+# ---- segment lengths, first-row parity, frame edges ----------------------------------------------------
+
+# (H, grid_blocks) -> classes the launch must contain, in both copies of the loop where it names both.
+# The strips of the clamped copy weigh 11/8 of the others, so at one grid they get shorter segments.
+#  (12, 0)   a block per unit of weight: one step per segment in the clamped strips (nothing staged is used), one
+#            or two in the others.
+#  (12, 30)  one and two steps (clamped), two and three (unaligned): the early-staged slots used exactly once; even
+#            and odd first rows; segments at the frame's first and last rows.
+#  (12, 20)  two and three steps (clamped), three and four (unaligned), both parities, both frame edges.
+#  (15, 25)  as (12, 20) with other cut rows.
+#  (13, 30)  an odd height: two and three steps in both copies.
+#  (20, 3)   fewer blocks than strips: long segments, blocks that cross from a strip's last row to the next strip's row 0.
+#  (40, 7)   long segments with cuts inside the strips.
+CLAIMS = {(12, 0): {"f:n1", "c:n1", "f:n2"},
+          (12, 30): {"f:n2", "c:n2", "f:n3", "f:even", "f:odd", "c:even", "c:odd", "f:row0", "c:row0", "f:last", "c:last"},
+          (12, 20): {"f:n3", "c:n3", "f:even", "f:odd", "c:even", "c:odd", "f:row0", "c:row0", "f:last", "c:last"},
+          (15, 25): {"f:n3", "c:n3", "f:odd", "c:odd"},
+          (13, 30): {"f:n2", "f:n3", "c:n2", "c:n3", "f:odd", "c:odd"},
+          (20, 3): {"next_strip", "f:n4+", "c:n4+", "f:row0", "f:last", "c:last"},
+          (40, 7): {"f:n4+", "c:n4+", "f:row0", "c:row0", "f:last", "c:last"}}
+
+
+@pytest.mark.parametrize("H,gb", sorted(CLAIMS))
+def test_segment_lengths(torch_dev, H, gb):
+    blocks = _blocks(H, gb)
+    assert CLAIMS[(H, gb)] <= _kinds(blocks, H), (H, gb, sorted(_kinds(blocks, H)), blocks)
+    if (H, gb) == (12, 0):  # no segment of the clamped strips has a second step
+        assert all(s[3] == 1 for b in blocks for s in b if not s[4])
+    L, R = _pair(H)
+    _both_modes(torch_dev, ("random", H), L, R, (gb,), f"H={H} random")
+    _both_modes(torch_dev, ("random", H), L, R, (gb,), f"H={H} random u=0", u=0)
+
+
+# ---- radii, disparity ranges ---------------------------------------------------------------------------
+
+@pytest.mark.parametrize("bs,d", [(1, 128), (5, 128), (7, 128), (9, 128), (11, 128), (15, 128), (9, 256)])
+def test_block_sizes(torch_dev, bs, d):
+    """R = 0, 2, 3, 4, 5: every build of the rotated loop (8 to 11 column chunks, the last one partial at odd R).
+    R = 7 (key-tree argmin, sequential loop) and D = 256 (two waves per block) are outside it: untouched guards."""
+    R = bs // 2
+    W = 256 if d == 128 else 384
+    for H, gb in ((12, 0), (13, 0), (20, 3)):
+        if gb == 0:  # two and three steps per segment: a block per two rows of the five strips
+            gb = 5 * H // 2 - (H == 13)
+        blocks = _blocks(H, gb, W=W, R=R, d=d)
+        kinds = _kinds(blocks, H)
+        if gb > 3:
+            assert "f:n2" in kinds and (H != 13 or {"f:n3", "f:odd"} <= kinds), (bs, H, gb, sorted(kinds))
+        else:
+            assert {"f:n4+", "next_strip"} <= kinds, (bs, H, gb, sorted(kinds))
+        L, Rr = _pair(H, W=W, d=d, seed=bs)
+        _both_modes(torch_dev, ("random", H, W, d, bs), L, Rr, (gb,), f"block {bs} D={d} H={H}", d=d, bs=bs)
+
+
+# ---- branches behind the chunks ------------------------------------------------------------------------
+
+def test_odd_disparity_count(torch_dev):
+    """D = 127: the high half of the last pair is overwritten through an exec-masked store between the box phase and
+    the staging's old place; uniqueness on (the block minima are read again behind the chunks) and off."""
+    d = 127
+    for H, gb in ((12, 30), (13, 20)):
+        kinds = _kinds(_blocks(H, gb, d=d), H)
+        assert {"f:n2", "c:n2"} <= kinds if H == 12 else {"f:n3", "f:odd"} <= kinds, sorted(kinds)
+        L, R = _pair(H, d=d, seed=127)
+        _both_modes(torch_dev, ("random127", H), L, R, (gb,), f"D=127 H={H}", d=d)
+        _both_modes(torch_dev, ("random127", H), L, R, (gb,), f"D=127 H={H} u=0", d=d, u=0)
+
+
+def test_no_subpixel(torch_dev):
+    """subpixel off: the sub-pixel stage's quotient is dropped for every pixel."""
+    H, gb = 13, 20
+    assert {"f:n3", "c:n3", "f:odd"} <= _kinds(_blocks(H, gb), H)
+    L, R = _pair(H)
+    want = _want(("random", H), L, R, M, D, BS, 10, False)
+    dL, dR = torch_dev.from_numpy(L).cuda(), torch_dev.from_numpy(R).cuda()
+    _run(torch_dev, dL, dR, L.shape, want, "subpixel off", (gb,), uniqueness_ratio=10, subpixel=False, **BASE)
+
+
+# ---- extreme images ------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("lv,rv", [(0, 255), (255, 0)])
+def test_extreme_images(torch_dev, lv, rv):
+    """All-0 against all-255: every column sum is at its bound, 9 * 255, every window sum at 81 * 255 = 20655, and a row
+    taken from the wrong slot (0 or 255 apart in every byte) cannot hide.  Then the same with the last rows swapped
+    between the views, so that entering and leaving rows differ by the full range."""
+    H = 13
+    for gb in (30, 20, 3):
+        kinds = _kinds(_blocks(H, gb), H)
+        assert ({"f:n2", "c:n2"} <= kinds) if gb == 30 else (("f:n3" in kinds) if gb == 20 else ("next_strip" in kinds))
+    L = np.full((H, W0), lv, np.uint8)
+    R = np.full((H, W0), rv, np.uint8)
+    _both_modes(torch_dev, ("flat", lv, rv), L, R, (30, 20, 3), f"flat {lv}/{rv}")
+    L2, R2 = L.copy(), R.copy()
+    L2[H // 2:], R2[H // 2:] = rv, lv
+    L2[::3, 5::7] = 128  # some texture: the minimum is not the same everywhere
+    _both_modes(torch_dev, ("step", lv, rv), L2, R2, (30, 20, 3), f"step {lv}/{rv}", u=0)
+
+
+# ---- batches and handles -------------------------------------------------------------------------------
+
+def test_batch_of_two_frames(torch_dev):
+    """Two frames per launch: ten and twenty blocks per frame put a segment boundary on the frame boundary; of three
+    blocks the middle one goes on from one frame into the next."""
+    torch = torch_dev
+    from depthestimation_amd.matcher import HipBlockMatcher
+    H = 12
+    fr = [_pair(H), _pair(H, seed=1)]
+    grids = (20, 40, 3)
+    k20, k40, k3 = (_kinds(_blocks(H, g, nf=2), H) for g in grids)
+    assert "frame_cut" in k20 and "f:n4+" in k20 and {"frame_cut", "f:n3", "c:n3"} <= k40 and "next_strip" in k3
+    assert any(len({s[0] for s in b}) == 2 for b in _blocks(H, 3, nf=2))  # a block with rows of both frames
+    dL = torch.from_numpy(np.stack([f[0] for f in fr])).cuda()
+    dR = torch.from_numpy(np.stack([f[1] for f in fr])).cuda()
+    wants = [_want(("random", H) if i == 0 else ("random1", H), L, R, M, D, BS, 10, True) for i, (L, R) in enumerate(fr)]
+    for g in grids:
+        mt = HipBlockMatcher(grid_blocks=g, uniqueness_ratio=10, **BASE)
+        try:
+            fx = torch.empty((2, H, W0), dtype=torch.int16, device="cuda")
+            fl = torch.empty((2, H, W0), dtype=torch.float32, device="cuda")
+            mt.compute_batch_device(dL, dR, out_fixed=fx, out_float=fl)
+            torch.cuda.synchronize()
+            for i in range(2):
+                _check_maps(fx[i], fl[i], wants[i], f"batch grid_blocks={g} frame={i}")
+        finally:
+            mt.close()
+
+
+def test_three_handles_in_flight(torch_dev):
+    """Three in_flight handles on three streams, four frames each, every output checked.  The grids are forced (the
+    handles' own rule gives a block per row at this size): segments of two, three and many steps."""
+    torch = torch_dev
+    from depthestimation_amd.matcher import HipBlockMatcher
+    H, NF = 12, 4
+    grids = (30, 20, 3)
+    assert "f:n2" in _kinds(_blocks(H, 30), H) and "f:n3" in _kinds(_blocks(H, 20), H) and "next_strip" in _kinds(_blocks(H, 3), H)
+    fr = [_pair(H, seed=s) for s in range(NF)]
+    keys = [("random", H), ("random1", H), ("random2", H), ("random3", H)]
+    wants = [_want(k, L, R, M, D, BS, 10, True) for k, (L, R) in zip(keys, fr)]
+    dev = [(torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda()) for L, R in fr]
+    mts = [HipBlockMatcher(in_flight=True, grid_blocks=g, uniqueness_ratio=10, **BASE) for g in grids]
+    sts = [torch.cuda.Stream() for _ in grids]
+    fx = [[torch.empty((H, W0), dtype=torch.int16, device="cuda") for _ in range(NF)] for _ in grids]
+    fl = [[torch.empty((H, W0), dtype=torch.float32, device="cuda") for _ in range(NF)] for _ in grids]
+    torch.cuda.synchronize()
+    try:
+        for i in range(NF):
+            for h, (mt, st) in enumerate(zip(mts, sts)):
+                mt.compute_device(dev[i][0], dev[i][1], out_fixed=fx[h][i], out_float=fl[h][i], stream=st)
+        torch.cuda.synchronize()
+        for h in range(len(grids)):
+            for i in range(NF):
+                _check_maps(fx[h][i], fl[h][i], wants[i], f"handle {h} (grid_blocks={grids[h]}) frame {i}")
+    finally:
+        for mt in mts:
+            mt.close()

@@ -7,7 +7,8 @@ loop of an instantiation (the unaligned-dword copy and the clamped-byte copy of 
   * counts of ds_read2_b64, ds_read_b64, v_mad_u64_u32 and s_waitcnt vmcnt(..);
   * where each vmcnt wait sits in the step, counted from the step's first global load: how many
     of the loop's global loads and global_store_* / global_atomic_* precede it (a wait behind all
-    of the stores is in the step's tail or at the next step's header);
+    of the stores is in the step's tail or at the next step's header), and, for the waits on the
+    store-taking path of a step, how many of the step's stores each one drains (store_drains below);
   * the ds_* instructions by opcode and the LDS-path cycles per wave they amount to (LDS_CYCLES below:
     cycles per wave-instruction for conflict-free accesses; a store's cycles are those of moving its
     address and data dwords to the LDS).  Static counts over every block of the loop, the branches a
@@ -19,7 +20,8 @@ loop of an instantiation (the unaligned-dword copy and the clamped-byte copy of 
 It reports; it gates nothing.
 
 usage:
-  python tools/rowloop_isa.py [c2 c2r c4 c5 c1 c3 ...] [--src <dsx_bm.hip>] [--tag <text>]
+  python tools/rowloop_isa.py [c2 c2r c4 c5 c1 c3 sad0 .. sad7 ...] [--src <dsx_bm.hip>] [--tag <text>]
+  (sad<R>: bm2<R, SAD, 1, 0>, the plain left pass of the pair layout at radius R)
 """
 from __future__ import annotations
 
@@ -90,6 +92,106 @@ def lines_of(body):
     return out
 
 
+def store_drains(ops, head):
+    """{op index: (k, text)} for the vmcnt waits on the store-taking path of one step of a row loop.
+
+    ops are the loop's (label, op, operands) in layout order, the header block included.  The step is walked from its
+    first global load (the first one the header reaches) round to that load again.  At a branch the walk takes the
+    side that still holds more global_store_* / global_atomic_* - the store-taking path - and between sides that hold
+    equally many the longer one (the work of a full step: a side that only skips something is not taken).  Inner
+    loops are passed once.  vmcnt counts loads and stores in order, so a vmcnt(n) wait retires all but the youngest n
+    of them: the wait is there for the youngest load it retires, and it drains the k stores issued behind that load
+    that it retires with it (every store it retires, where it retires no load).  The walk goes round twice and
+    reports the second time, when the stores of the previous step's tail are in the queue.  Static: a side that the
+    kernel only takes on steps without stores (a first step's staging behind the box phase, where the build has one)
+    is not known to be such, is walked behind the stores and reported as draining them."""
+    at = {}
+    for k, (lab, _, _) in enumerate(ops):
+        at.setdefault(lab, k)
+    n = len(ops)
+    is_load = lambda k: ops[k][1].startswith("global_load")  # noqa: E731
+    is_store = lambda k: ops[k][1].startswith(("global_store", "global_atomic"))  # noqa: E731
+
+    def succ(k):
+        _, op, arg = ops[k]
+        s = []
+        if op != "s_branch" and op != "s_endpgm" and k + 1 < n:
+            s.append(k + 1)
+        if op.startswith(("s_cbranch", "s_branch")):
+            t = re.search(r"(\.LBB\d+_\d+)", arg)
+            if t and t.group(1) in at:
+                s.append(at[t.group(1)])
+        return s
+
+    if head not in at:
+        return {}
+    seen, todo, first = set(), [at[head]], []
+    while todo:
+        k = todo.pop()
+        if k in seen:
+            continue
+        seen.add(k)
+        if is_load(k):
+            first.append(k)
+            continue
+        todo.extend(succ(k))
+    if not first:
+        return {}
+    start = min(first)
+    # value of the best way on from op k: (stores ahead, length), ways into the start or out of the loop end
+    val, state, stack = {}, {}, [(start, iter(succ(start)))]
+    better = lambda a, b: a > b  # noqa: E731  (stores ahead, then length)
+    best_of, acc = {start: None}, {start: None}
+    state[start] = 1
+    while stack:
+        k, it = stack[-1]
+        nxt = next(it, None)
+        if nxt is None:
+            stack.pop()
+            a = acc[k] or (0, 0)
+            val[k] = (a[0] + (1 if is_store(k) else 0), a[1] + 1)
+            state[k] = 2
+            if stack:
+                p = stack[-1][0]
+                if acc[p] is None or better(val[k], acc[p]):
+                    acc[p], best_of[p] = val[k], k
+            continue
+        if nxt == start or state.get(nxt) == 1:  # round the step, or an inner loop's back edge
+            if nxt == start and (acc[k] is None or better((0, 0), acc[k])):
+                acc[k], best_of[k] = (0, 0), start
+            continue
+        if state.get(nxt) == 2:
+            if acc[k] is None or better(val[nxt], acc[k]):
+                acc[k], best_of[k] = val[nxt], nxt
+            continue
+        state[nxt] = 1
+        acc[nxt], best_of[nxt] = None, None
+        stack.append((nxt, iter(succ(nxt))))
+    path, k = [], start
+    while k is not None and (k != start or not path) and len(path) <= n:
+        path.append(k)
+        k = best_of.get(k)
+    found, queue = {}, []
+    for lap in range(2):
+        for k in path:
+            if is_load(k):
+                queue.append("L")
+            elif is_store(k):
+                queue.append("S")
+            elif ops[k][1] == "s_waitcnt" and "vmcnt" in ops[k][2]:
+                v = int(re.search(r"vmcnt\((\d+)\)", ops[k][2]).group(1))
+                gone = queue[:max(0, len(queue) - v)]
+                queue = queue[len(gone):]
+                if lap:
+                    if "L" in gone:
+                        d = gone[len(gone) - gone[::-1].index("L"):].count("S")
+                        found[k] = (d, f"drains {d} stores")
+                    else:
+                        d = gone.count("S")
+                        found[k] = (d, f"drains {d} stores (retires no load)")
+    return found
+
+
 def report(asm, name, out):
     r, ssd, nw, side, abs_ = BENCH_KERNELS[name]
     sym = symbol(r, ssd, nw, side, abs_)
@@ -146,15 +248,31 @@ def report(asm, name, out):
         head = ".L" + max(set(hdr), key=hdr.count) if hdr else ops[0][0]
         after_store = reach([k + 1 for k, (_, op, _) in enumerate(ops) if op.startswith(("global_store", "global_atomic"))], loads)
         at_header = reach([at[head]], loads | lds) if head in at else set()
+        # "follows a store" is positional.  What costs is a wait that retires a store of the step with the load it is
+        # there for: store_drains walks the store-taking path of a step, over the whole loop - the blocks above plus
+        # every block that names the header as its loop (a rotated loop's header and latch lie outside the range).
+        texts = {b.split(":")[0]: b for b in re.split(r"\n(?=\.LBB\d+_\d+:)", body)}
+        mine = re.compile(r"(Header=|Parent Loop )" + re.escape(head[2:]) + r"\b")
+        wlabs = labs | {b[0] for b in bl if b[0] == head or mine.search(texts.get(b[0], ""))}
+        wops = [(g, lab, op, arg) for g, (lab, op, arg) in enumerate(ln) if lab in wlabs]
+        found = {wops[k][0]: v for k, v in store_drains([w[1:] for w in wops], head).items()}
+        gidx = [g for g, (lab, _, _) in enumerate(ln) if lab in labs]
         waits = []
         for k, (lab, op, arg) in enumerate(ops):
             if op == "s_waitcnt" and "vmcnt" in arg:
                 v = re.search(r"vmcnt\((\d+)\)", arg).group(1)
                 where = [w for w, c in (("at the loop header", k in at_header), ("follows a store of the step", k in after_store)) if c]
-                waits.append(f"    vmcnt({v}) in {lab}: {', '.join(where) or 'between the prefetch and the stores'}")
+                d = found.get(gidx[k])
+                waits.append(f"    vmcnt({v}) in {lab}: {', '.join(where) or 'between the prefetch and the stores'}; "
+                             + (d[1] if d else "not on the store-taking path"))
         out(f"    s_waitcnt vmcnt: {len(waits)}")
         for w in waits:
             out(w)
+        extra = [(g, lab, arg) for g, lab, op, arg in wops if g in found and lab not in labs]
+        for g, lab, arg in extra:
+            out(f"    {arg.strip()} in {lab} (a block of the loop outside the range above): {found[g][1]}")
+        worst = max((d for d, _ in found.values()), default=0)
+        out(f"    store-taking path: {len(found)} vmcnt waits, " + (f"the worst drains {worst} stores" if worst else "none drains a store"))
 
 
 def segstart_report(asm, name, out):
@@ -256,6 +374,9 @@ def main(argv):
         else:
             names.append(a)
     names = names or ORDER
+    for n in names:  # sad<R>: the plain left pass of the pair layout at radius R, bm2<R, SAD, 1, 0>
+        if re.fullmatch(r"sad[0-7]", n):
+            BENCH_KERNELS.setdefault(n, (int(n[3]), False, 1, 0, False))
     out = print
     if tag:
         out(f"== {tag} ==")
