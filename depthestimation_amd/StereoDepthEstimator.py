@@ -40,6 +40,12 @@ class StereoDepthEstimator:
     def get_sgbm_params(self) -> Dict[str, int]:
         return self.core.get_sgbm_params()
 
+    @property
+    def confidence_map(self):
+        """The last estimate's peak-ratio confidence map (uint8, cropped like the disparity) when
+        ``configure_sgbm(confidence=True)``; None otherwise.  Read-only."""
+        return self.core.confidence_map
+
     def estimate_depth(self) -> Tuple[np.ndarray, Optional[np.ndarray]]:
         """StereoDepthEstimator.py:90-107."""
         if self.left_source is None or self.right_source is None:

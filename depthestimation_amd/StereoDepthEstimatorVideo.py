@@ -13,6 +13,9 @@ torch.distributed env) to process only frames i with i % world_size == rank in o
 GPU (``sharding.py``); or pass ``devices=[0, 1, ...]`` to drive several GPUs from this one
 process (``multigpu.DepthPipeline`` per device: frame i on devices[i % N], several frames in flight
 per device, results yielded in frame order).
+
+``configure_sgbm(confidence_threshold=t)`` is honoured by every form; the generator yields depth maps only
+and returns no confidence map.
 """
 from __future__ import annotations
 

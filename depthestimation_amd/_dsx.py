@@ -44,6 +44,8 @@ EXPORTS = (
     "dsx_texture_sum_device", "dsx_census_device",
     "dsx_default_refine", "dsx_check_refine", "dsx_wmedian_weights", "dsx_wmedian_device",
     "dsx_postprocess_refine_device", "dsx_process_pair_refine_device",
+    "dsx_default_confidence", "dsx_check_confidence", "dsx_set_confidence", "dsx_compute_conf_device",
+    "dsx_compute_conf_host",
 )
 
 
@@ -87,6 +89,18 @@ class DsxPrefilter(ctypes.Structure):
         ("cap", ctypes.c_int32),
         ("texture_threshold", ctypes.c_int32),
         ("reserved", ctypes.c_int32 * 4),
+    ]
+
+
+CONFIDENCE = {"peak_ratio": 1}  # DSX_CONF_* (include/dsx.h)
+
+
+class DsxConfidence(ctypes.Structure):
+    """dsx_confidence (include/dsx.h): the matcher's confidence measure and its threshold."""
+    _fields_ = [
+        ("type", ctypes.c_int32),
+        ("threshold", ctypes.c_int32),
+        ("reserved", ctypes.c_int32 * 6),
     ]
 
 
@@ -152,8 +166,14 @@ def _bind(lib):
     P = ctypes.POINTER(DsxParams)
     F = ctypes.POINTER(DsxPrefilter)
     RF = ctypes.POINTER(DsxRefine)
+    CF = ctypes.POINTER(DsxConfidence)
     PP = ctypes.POINTER(DsxPostParams)
     sig = {
+        "dsx_default_confidence": (None, [CF]),
+        "dsx_check_confidence": (ctypes.c_int, [P, CF]),
+        "dsx_set_confidence": (ctypes.c_int, [vp, CF]),
+        "dsx_compute_conf_device": (ctypes.c_int, [vp, vp, vp, i32, i32, i64, vp, vp, vp, vp]),
+        "dsx_compute_conf_host": (ctypes.c_int, [vp, vp, vp, i32, i32, i64, vp, vp, vp]),
         "dsx_default_refine": (None, [RF]),
         "dsx_check_refine": (ctypes.c_int, [RF]),
         "dsx_wmedian_weights": (ctypes.c_int, [i32, ctypes.POINTER(ctypes.c_uint16)]),
@@ -319,6 +339,17 @@ def make_prefilter(prefilter_type="none", prefilter_size=9, prefilter_cap=31, te
     f.cap = int(prefilter_cap)
     f.texture_threshold = int(texture_threshold)
     return f
+
+
+def make_confidence(confidence_threshold=0) -> DsxConfidence:
+    """dsx_confidence from the matcher keyword; ValueError for a non-integer or a value outside [0, 255]."""
+    c = DsxConfidence()
+    lib().dsx_default_confidence(ctypes.byref(c))
+    if isinstance(confidence_threshold, bool) or int(confidence_threshold) != confidence_threshold:
+        raise ValueError("confidence_threshold must be an integer in [0, 255]")
+    c.threshold = int(confidence_threshold)
+    check(lib().dsx_check_confidence(None, ctypes.byref(c)), "dsx_check_confidence")
+    return c
 
 
 def make_refine(refine="none", refine_radius=5, refine_sigma=8, refine_fill=True) -> DsxRefine:

@@ -159,6 +159,22 @@ int check_prefilter(const dsx_params *p, const dsx_prefilter *f) {
     return DSX_OK;
 }
 
+// p may be NULL (the set's own ranges only)
+int check_confidence(const dsx_params *p, const dsx_confidence *c) {
+    if (!c) return fail(DSX_EINVAL, "confidence is NULL");
+    if (c->type != DSX_CONF_PEAK_RATIO) return fail(DSX_EINVAL, "confidence type must be PEAK_RATIO (1)");
+    if (c->threshold < 0 || c->threshold > 255) return fail(DSX_EINVAL, "confidence threshold must be in [0, 255]");
+    if (p) return check(p);
+    return DSX_OK;
+}
+
+// The geometry a handle's volume-path launches use: the fused handle's own, except BM_SAD1 (see dsx_handle.gv).
+void pick_volume_geometry(const dsx_params &p, dsx::Geometry &g) {
+    dsx_params q = p;
+    q.path = DSX_PATH_VOLUME;
+    pick_geometry(q, g);
+}
+
 struct TimedLaunch {
     int kernel;
     hipEvent_t a, b;
@@ -170,7 +186,11 @@ struct dsx_handle {
     int device = 0;
     dsx_params p{};
     dsx_prefilter pf{};  // type NONE: no filter, no mask, no buffer
+    dsx_confidence cf{};  // threshold 0: no effect
     dsx::Geometry g{};
+    // geometry of the volume path: g, except on a fused SAD handle with D <= 64 (BM_SAD1), whose confidence
+    // calls run K1 / K2 in the pair layout the volume path always has
+    dsx::Geometry gv{};
     hipStream_t stream = nullptr;  // for dsx_compute_host
     // buffer cache keyed by (H, W, geometry); single entry like RectificationCache (rectify.py:49-50)
     int cH = 0, cW = 0, cDp = 0, cCostBytes = 0;
@@ -191,6 +211,8 @@ struct dsx_handle {
     int16_t *dFixed = nullptr;
     float *dFloat = nullptr;
     size_t stagingBytes = 0;     // dL + dR + dFixed + dFloat (dsx_compute_host)
+    uint8_t *dConf = nullptr;    // dsx_compute_conf_host: the confidence map
+    size_t dConfBytes = 0;
     uint8_t *pfBuf = nullptr;    // prefilter: the filtered left views of every frame, then the right views
     size_t pfBytes = 0;          //   (rows pf_pitch(W) apart)
     uint32_t *lrKeys = nullptr;  // LR check: right-view winner keys per pixel (atomicMin target)
@@ -232,6 +254,9 @@ void free_buffers(dsx_handle *h) {
     (void)hipFree(h->dR);
     (void)hipFree(h->dFixed);
     (void)hipFree(h->dFloat);
+    (void)hipFree(h->dConf);
+    h->dConf = nullptr;
+    h->dConfBytes = 0;
     (void)hipFree(h->pfBuf);
     h->pfBuf = nullptr;
     h->pfBytes = 0;
@@ -304,7 +329,8 @@ int grow(T *&buf, size_t &held, size_t need) {
     return DSX_OK;
 }
 
-int ensure_buffers(dsx_handle *h, int H, int W, bool host_staging, int nframes = 1) {
+// conf: the call runs the confidence variant (a confidence output, or the handle's threshold > 0)
+int ensure_buffers(dsx_handle *h, int H, int W, bool host_staging, int nframes = 1, bool conf = false) {
     const int cbytes = h->p.cost == DSX_COST_SSD ? 4 : 2;
     if (h->cH != H || h->cW != W || h->cDp != h->g.Dp || h->cCostBytes != cbytes) free_buffers(h);
     const size_t n = (size_t)H * W;
@@ -343,7 +369,7 @@ int ensure_buffers(dsx_handle *h, int H, int W, bool host_staging, int nframes =
     if (h->pf.type != DSX_PREFILTER_NONE &&
         (rc = grow(h->pfBuf, h->pfBytes, 2 * (size_t)nframes * H * (size_t)pf_pitch(W))))
         return rc;
-    if (!fused && (rc = grow(h->vol, h->vol_bytes, n * h->g.Dp * cbytes))) return rc;
+    if ((!fused || conf) && (rc = grow(h->vol, h->vol_bytes, n * h->gv.Dp * cbytes))) return rc;
     if (bt && (rc = grow(h->btWs, h->btWsBytes, dsx::bt_workspace(H, W, h->g.Dp)))) return rc;
     if (is_census(h->p.cost) &&
         (rc = grow(h->censusWs, h->censusWsBytes, 2 * n * dsx::census_code_bytes(h->p.cost))))
@@ -376,8 +402,8 @@ int ensure_buffers(dsx_handle *h, int H, int W, bool host_staging, int nframes =
     return DSX_OK;
 }
 
-uint32_t pad_value(dsx_handle *h) {
-    const uint32_t keymax = (uint32_t)((1ull << (32 - h->g.DB)) - 1ull);
+uint32_t pad_value(dsx_handle *h, int DB) {
+    const uint32_t keymax = (uint32_t)((1ull << (32 - DB)) - 1ull);
     return h->p.cost == DSX_COST_SSD ? keymax : (keymax < 0xFFFFu ? keymax : 0xFFFFu);
 }
 
@@ -489,7 +515,7 @@ dsx::Bm2Args base_args(dsx_handle *h, int H, int W, int64_t stride, const DsxEnv
     a.lr = h->p.disp12_max_diff;
     a.subpix = h->p.subpixel;
     a.float_mode = h->p.float_mode;
-    a.padv = pad_value(h);
+    a.padv = pad_value(h, h->g.DB);
     a.strip_begin = 0;
     a.strip_count = (W + dsx::kStripWidth - 1) / dsx::kStripWidth;
     a.grid_override = h->p.grid_blocks;
@@ -562,6 +588,9 @@ int check_fill_shape(int64_t H, int64_t W) {
     return DSX_OK;
 }
 
+// A call runs K2's confidence variant when it is handed a map or the handle's threshold is on.
+bool conf_call(const dsx_handle *h, const void *outConf) { return outConf != nullptr || h->cf.threshold > 0; }
+
 // Orders a call that touches handle scratch on `st` after the previous such call on another stream.
 int wait_scratch(dsx_handle *h, hipStream_t st) {
     if (h->scratchPending && h->scratchStream != st) DSX_HIP(hipStreamWaitEvent(st, h->scratchDone, 0));
@@ -633,14 +662,17 @@ int run_right_pass(dsx_handle *h, const void *dL, const void *dR, int H, int W, 
 // kernel (spk_tile applies it while loading the map): no lr_fixup launch; h->lastKeys / lastDstar
 // name this call's key half and winners.
 int run(dsx_handle *h, const void *dL, const void *dR, int H, int W, int64_t stride, void *outFixed, void *outFloat,
-        hipStream_t st, int nframes = 1, int64_t frame_stride = 0, bool defer_lr = false) {
+        hipStream_t st, int nframes = 1, int64_t frame_stride = 0, bool defer_lr = false, void *outConf = nullptr) {
     const int radius = h->p.block_size / 2;
     const bool ssd = h->p.cost == DSX_COST_SSD;
     const bool bt = h->p.cost == DSX_COST_BT;  // BT costs exist only as a volume
     // sgbm_post: the matcher writes int16 maps into postIn, the tail then writes the outputs
     void *const finalFixed = outFixed, *const finalFloat = outFloat;
     const bool census = is_census(h->p.cost);  // so do census costs
-    const bool fused = h->p.path == DSX_PATH_FUSED && !h->p.aggregation && !volume_only(h->p.cost);
+    // the confidence variant lives in K2: such a call runs the volume path on any handle
+    const bool conf = conf_call(h, outConf);
+    const bool fused = h->p.path == DSX_PATH_FUSED && !h->p.aggregation && !volume_only(h->p.cost) && !conf;
+    const dsx::Geometry &gv = h->gv;
     const bool lr_sg = h->p.lr_form == DSX_LR_FORM_SGBM;  // OpenCV's LR form (always on)
     const bool pf = h->pf.type != DSX_PREFILTER_NONE;  // the filtered images are handle scratch too
     const bool scratch = h->p.disp12_max_diff >= 0 || lr_sg || !fused || h->p.sgbm_post || pf;
@@ -769,9 +801,9 @@ int run(dsx_handle *h, const void *dL, const void *dR, int H, int W, int64_t str
                 b.W = W;
                 b.m = h->p.min_disp;
                 b.D = h->p.num_disp;
-                b.Dp = h->g.Dp;
+                b.Dp = gv.Dp;
                 b.R = radius;
-                b.padv = pad_value(h);
+                b.padv = pad_value(h, gv.DB);
                 DSX_LAUNCH(h, "bt_hsum", st, dsx::launch_bt_volume(b, 0, st));
                 DSX_LAUNCH(h, "bt_vsum", st, dsx::launch_bt_volume(b, 1, st));
             } else if (census) {
@@ -796,11 +828,11 @@ int run(dsx_handle *h, const void *dL, const void *dR, int H, int W, int64_t str
                 v.W = W;
                 v.m = h->p.min_disp;
                 v.D = h->p.num_disp;
-                v.Dp = h->g.Dp;
+                v.Dp = gv.Dp;
                 v.R = radius;
                 v.window = h->p.cost;
                 v.seg = census_seg();
-                v.padv = pad_value(h);
+                v.padv = pad_value(h, gv.DB);
                 DSX_LAUNCH(h, "census_volume", st, dsx::launch_census_volume(v, st));
             } else {
                 dsx::Bm2Args a = base_args(h, H, W, stride);
@@ -808,7 +840,8 @@ int run(dsx_handle *h, const void *dL, const void *dR, int H, int W, int64_t str
                 a.ref = static_cast<const uint8_t *>(dL) + f * frame_stride;
                 a.src = static_cast<const uint8_t *>(dR) + f * frame_stride;
                 a.vol = h->vol;
-                DSX_LAUNCH(h, "cost_volume", st, dsx::launch_bm2(radius, ssd ? dsx::BM_SSD : dsx::BM_SAD, h->g.NW, a, st));
+                a.padv = pad_value(h, gv.DB);
+                DSX_LAUNCH(h, "cost_volume", st, dsx::launch_bm2(radius, ssd ? dsx::BM_SSD : dsx::BM_SAD, gv.NW, a, st));
             }
             const bool agg = h->p.aggregation != DSX_AGG_NONE;
             const bool agg_all = agg && sgm_concurrent(h);
@@ -855,14 +888,14 @@ int run(dsx_handle *h, const void *dL, const void *dR, int H, int W, int64_t str
             dsx::VolArgs v{};
             v.vol = agg_all ? static_cast<const void *>(h->sgmL) : (agg ? static_cast<const void *>(h->sgmS) : h->vol);
             v.nsum = agg_all ? nd : 0;
-            v.sstride = (size_t)H * W * h->g.Dp;
+            v.sstride = (size_t)H * W * gv.Dp;
             v.H = H;
             v.W = W;
             v.m = h->p.min_disp;
             v.D = h->p.num_disp;
-            v.Dp = h->g.Dp;
-            v.DB = h->g.DB;
-            v.TPP = h->g.TPP;
+            v.Dp = gv.Dp;
+            v.DB = gv.DB;
+            v.TPP = gv.TPP;
             v.uniq = h->p.uniqueness_ratio;
             v.lr = h->p.disp12_max_diff;
             v.lr_form = h->p.lr_form;
@@ -870,13 +903,16 @@ int run(dsx_handle *h, const void *dL, const void *dR, int H, int W, int64_t str
             v.float_mode = h->p.float_mode;
             v.out_fixed = outFixed ? static_cast<int16_t *>(outFixed) + fo : nullptr;
             v.out_float = outFloat ? static_cast<float *>(outFloat) + fo : nullptr;
+            v.conf = conf ? 1 : 0;
+            v.conf_t = h->cf.threshold;
+            v.out_conf = outConf ? static_cast<uint8_t *>(outConf) + fo : nullptr;
             const bool wide = ssd || agg;  // u32 costs: SSD block costs or SGM path sums
-            if (dsx::volume_smem_bytes(h->g.TX, wide, h->g.Dp, h->g.TPP, W) > 160 * 1024)
+            if (dsx::volume_smem_bytes(gv.TX, wide, gv.Dp, gv.TPP, W, conf) > 160 * 1024)
                 return fail(DSX_EINVAL, "image too wide for the volume path's row kernel");
-            DSX_LAUNCH(h, "volume_wta", st, dsx::launch_volume_wta(h->g.TX, wide, v, st));
+            DSX_LAUNCH(h, "volume_wta", st, dsx::launch_volume_wta(gv.TX, wide, v, st));
         }
     }
-    if (pf && h->pf.texture_threshold > 0) {
+    if (pf && h->pf.texture_threshold > 0 && (outFixed || outFloat)) {  // a map-only confidence call has neither
         // after the last matcher kernel (uniqueness, sub-pixel, LR check), before the sgbm_post tail
         dsx::TextureArgs t{};
         t.pref = texL;
@@ -912,6 +948,28 @@ int check_shape(int H, int W, int64_t stride) {
     if (H <= 0 || W <= 0) return fail(DSX_EINVAL, "image must be non-empty");
     if (stride < W) return fail(DSX_EINVAL, "stride_bytes must be >= W");
     if ((int64_t)H * W > (int64_t)1 << 31) return fail(DSX_EINVAL, "image too large");
+    return DSX_OK;
+}
+
+// dsx_compute_host / dsx_compute_conf_host after their argument checks (out_fixed may be NULL only with out_conf)
+int compute_host(dsx_handle *h, const uint8_t *L, const uint8_t *R, int H, int W, int64_t stride_bytes,
+                 int16_t *out_fixed, float *out_float, uint8_t *out_conf) {
+    int rc = check_shape(H, W, stride_bytes);
+    if (rc) return rc;
+    DSX_HIP(hipSetDevice(h->device));
+    rc = ensure_buffers(h, H, W, true, 1, conf_call(h, out_conf));
+    if (rc) return rc;
+    if (out_conf && (rc = grow(h->dConf, h->dConfBytes, (size_t)H * W))) return rc;
+    hipStream_t st = h->stream;
+    DSX_HIP(hipMemcpy2DAsync(h->dL, W, L, stride_bytes, W, H, hipMemcpyHostToDevice, st));
+    DSX_HIP(hipMemcpy2DAsync(h->dR, W, R, stride_bytes, W, H, hipMemcpyHostToDevice, st));
+    rc = run(h, h->dL, h->dR, H, W, W, h->dFixed, out_float ? h->dFloat : nullptr, st, 1, 0, false,
+             out_conf ? h->dConf : nullptr);
+    if (rc) return rc;
+    if (out_fixed) DSX_HIP(hipMemcpyAsync(out_fixed, h->dFixed, (size_t)H * W * 2, hipMemcpyDeviceToHost, st));
+    if (out_float) DSX_HIP(hipMemcpyAsync(out_float, h->dFloat, (size_t)H * W * 4, hipMemcpyDeviceToHost, st));
+    if (out_conf) DSX_HIP(hipMemcpyAsync(out_conf, h->dConf, (size_t)H * W, hipMemcpyDeviceToHost, st));
+    DSX_HIP(hipStreamSynchronize(st));
     return DSX_OK;
 }
 
@@ -983,7 +1041,9 @@ int dsx_create(int device, const dsx_params *p, dsx_handle **out) {
     dsx_handle *h = new dsx_handle();
     h->device = device;
     h->p = *p;
+    dsx_default_confidence(&h->cf);
     pick_geometry(*p, h->g);
+    pick_volume_geometry(*p, h->gv);
     hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         delete h;
@@ -1008,6 +1068,7 @@ int dsx_set_params(dsx_handle *h, const dsx_params *p) {
     DSX_HIP(hipStreamSynchronize(h->stream));
     h->p = *p;
     pick_geometry(*p, h->g);
+    pick_volume_geometry(*p, h->gv);
     return DSX_OK;
 }
 
@@ -1117,9 +1178,50 @@ int dsx_compute_device(dsx_handle *h, const void *dL, const void *dR, int32_t H,
     int rc = check_shape(H, W, stride_bytes);
     if (rc) return rc;
     DSX_HIP(hipSetDevice(h->device));
-    rc = ensure_buffers(h, H, W, false);
+    rc = ensure_buffers(h, H, W, false, 1, conf_call(h, nullptr));
     if (rc) return rc;
     return run(h, dL, dR, H, W, stride_bytes, d_out_fixed, d_out_float, static_cast<hipStream_t>(hip_stream));
+}
+
+void dsx_default_confidence(dsx_confidence *c) {
+    if (!c) return;
+    std::memset(c, 0, sizeof(*c));
+    c->type = DSX_CONF_PEAK_RATIO;
+    c->threshold = 0;
+}
+
+int dsx_check_confidence(const dsx_params *p, const dsx_confidence *c) {
+    g_err.clear();
+    return check_confidence(p, c);
+}
+
+int dsx_set_confidence(dsx_handle *h, const dsx_confidence *c) {
+    g_err.clear();
+    if (!h) return fail(DSX_EINVAL, "handle is NULL");
+    dsx_confidence off;
+    dsx_default_confidence(&off);
+    if (!c) c = &off;
+    int rc = check_confidence(nullptr, c);
+    if (rc) return rc;
+    DSX_HIP(hipSetDevice(h->device));
+    DSX_HIP(hipStreamSynchronize(h->stream));
+    h->cf = *c;
+    return DSX_OK;
+}
+
+int dsx_compute_conf_device(dsx_handle *h, const void *dL, const void *dR, int32_t H, int32_t W, int64_t stride_bytes,
+                            void *d_out_fixed, void *d_out_float, void *d_out_conf, void *hip_stream) {
+    if (!d_out_conf) return dsx_compute_device(h, dL, dR, H, W, stride_bytes, d_out_fixed, d_out_float, hip_stream);
+    g_err.clear();
+    if (!h) return fail(DSX_EINVAL, "handle is NULL");
+    if (!dL || !dR) return fail(DSX_EINVAL, "input pointers are NULL");
+    int rc = check_shape(H, W, stride_bytes);
+    if (rc) return rc;
+    DSX_HIP(hipSetDevice(h->device));
+    rc = ensure_buffers(h, H, W, false, 1, true);
+    if (rc) return rc;
+    return run(h, dL, dR, H, W, stride_bytes, d_out_fixed, d_out_float, static_cast<hipStream_t>(hip_stream), 1, 0, false,
+               d_out_conf);
 }
 
 int dsx_postprocess_fast_device(const void *d_disp, int32_t H, int32_t W, int64_t in_pitch, int32_t crop,
@@ -1462,7 +1564,7 @@ int dsx_compute_batch_device(dsx_handle *h, int32_t nframes, const void *dL, con
     if ((int64_t)nframes * H * W > ((int64_t)1 << 31) - 1)
         return fail(DSX_EINVAL, "nframes * H * W must stay below 2^31 pixels per launch");
     DSX_HIP(hipSetDevice(h->device));
-    rc = ensure_buffers(h, H, W, false, nframes);
+    rc = ensure_buffers(h, H, W, false, nframes, conf_call(h, nullptr));
     if (rc) return rc;
     return run(h, dL, dR, H, W, stride_bytes, d_out_fixed, d_out_float, static_cast<hipStream_t>(hip_stream), nframes,
                frame_stride_bytes);
@@ -1486,20 +1588,16 @@ int dsx_compute_host(dsx_handle *h, const uint8_t *L, const uint8_t *R, int32_t 
     g_err.clear();
     if (!h) return fail(DSX_EINVAL, "handle is NULL");
     if (!L || !R || !out_fixed) return fail(DSX_EINVAL, "NULL argument (out_fixed is required)");
-    int rc = check_shape(H, W, stride_bytes);
-    if (rc) return rc;
-    DSX_HIP(hipSetDevice(h->device));
-    rc = ensure_buffers(h, H, W, true);
-    if (rc) return rc;
-    hipStream_t st = h->stream;
-    DSX_HIP(hipMemcpy2DAsync(h->dL, W, L, stride_bytes, W, H, hipMemcpyHostToDevice, st));
-    DSX_HIP(hipMemcpy2DAsync(h->dR, W, R, stride_bytes, W, H, hipMemcpyHostToDevice, st));
-    rc = run(h, h->dL, h->dR, H, W, W, h->dFixed, out_float ? h->dFloat : nullptr, st);
-    if (rc) return rc;
-    DSX_HIP(hipMemcpyAsync(out_fixed, h->dFixed, (size_t)H * W * 2, hipMemcpyDeviceToHost, st));
-    if (out_float) DSX_HIP(hipMemcpyAsync(out_float, h->dFloat, (size_t)H * W * 4, hipMemcpyDeviceToHost, st));
-    DSX_HIP(hipStreamSynchronize(st));
-    return DSX_OK;
+    return compute_host(h, L, R, H, W, stride_bytes, out_fixed, out_float, nullptr);
+}
+
+int dsx_compute_conf_host(dsx_handle *h, const uint8_t *L, const uint8_t *R, int32_t H, int32_t W, int64_t stride_bytes,
+                          int16_t *out_fixed, float *out_float, uint8_t *out_conf) {
+    if (!out_conf) return dsx_compute_host(h, L, R, H, W, stride_bytes, out_fixed, out_float);
+    g_err.clear();
+    if (!h) return fail(DSX_EINVAL, "handle is NULL");
+    if (!L || !R) return fail(DSX_EINVAL, "input pointers are NULL");
+    return compute_host(h, L, R, H, W, stride_bytes, out_fixed, out_float, out_conf);
 }
 
 int dsx_fill_holes_status(void) {
@@ -1586,7 +1684,7 @@ int dsx_process_pair_refine_device(dsx_handle *h, const void *dL, const void *dR
         if (rc) return rc;
     }
     DSX_HIP(hipSetDevice(h->device));
-    rc = ensure_buffers(h, H, W, false);
+    rc = ensure_buffers(h, H, W, false, 1, conf_call(h, nullptr));
     if (rc) return rc;
     const size_t n = (size_t)H * W;
     const bool full = pp->mode == DSX_POST_FULL;
@@ -1620,7 +1718,7 @@ int dsx_process_pair_refine_device(dsx_handle *h, const void *dL, const void *dR
         // the fused pass's LR check moves into the speckle pass's loads (no lr_fixup launch) when that
         // pass is the two-launch form and the matcher is the fused pass with a check
         const bool fusedp = h->p.path == DSX_PATH_FUSED && !h->p.aggregation && !volume_only(h->p.cost) &&
-                            !h->p.sgbm_post;
+                            !h->p.sgbm_post && !conf_call(h, nullptr);  // a threshold: the volume path
         const bool lrc = h->p.lr_form == DSX_LR_FORM_SGBM || h->p.disp12_max_diff >= 0;
         // a texture threshold masks the checked map: the fix-up runs in run(), then the mask
         defer = fusedp && lrc && dsx::post_full_two_launch(a) && h->pf.texture_threshold == 0 &&
@@ -1714,7 +1812,7 @@ int dsx_reset_times(dsx_handle *h) {
 
 int dsx_workspace_bytes(dsx_handle *h, int64_t *bytes) {
     if (!h || !bytes) return fail(DSX_EINVAL, "NULL argument");
-    *bytes = (int64_t)(h->stagingBytes + h->pfBytes + h->lrKeysBytes + h->dStarBytes + h->vol_bytes + h->btWsBytes + h->censusWsBytes +
+    *bytes = (int64_t)(h->stagingBytes + h->dConfBytes + h->pfBytes + h->lrKeysBytes + h->dStarBytes + h->vol_bytes + h->btWsBytes + h->censusWsBytes +
                        h->postInBytes + h->postWsBytes + h->sgmSBytes + h->sgmLBytes + h->ppDispBytes +
                        h->ppFixedBytes + h->ppWsBytes);
     return DSX_OK;

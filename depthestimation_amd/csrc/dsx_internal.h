@@ -64,6 +64,10 @@ struct VolArgs {
     int lr_form;      // DSX_LR_FORM_BM: right-view argmin over every cost; DSX_LR_FORM_SGBM: OpenCV's form
     int16_t *out_fixed;
     float *out_float;
+    // confidence variant of K2 (dsx_confidence of dsx.h): conf selects it; out_conf (uint8 H x W, may be
+    // null) takes the peak-ratio map; pixels with q < conf_t get the invalid value after the LR test
+    int conf, conf_t;
+    uint8_t *out_conf;
 };
 
 constexpr int kStripWidth = 32;  // TX of bm2
@@ -101,7 +105,7 @@ hipError_t launch_lr_fixup(const int16_t *dstar, const uint32_t *keys, uint32_t 
 hipError_t launch_lr_fixup_sgbm(const int16_t *fixed, const uint32_t *keys, int rows, int W, int m, int lr,
                                 int kshift, int16_t *out_fixed, float *out_float, hipStream_t st);
 
-size_t volume_smem_bytes(int TX, bool ssd, int Dp, int TPP, int W);
+size_t volume_smem_bytes(int TX, bool ssd, int Dp, int TPP, int W, bool conf = false);
 
 // Semi-global aggregation (dsx_sgm.hip): one launch per path direction over the K1 volume.
 struct SgmArgs {

@@ -75,8 +75,25 @@ __device__ __forceinline__ uint32_t slice_cost(const uint4 (&v)[NV], int j) {
 
 // LRM: 0 no left-right check, 1 the A5' form (right-view argmin over every cost), 2 OpenCV
 // StereoSGBM's form (disp2 from the unique left winners, floor / ceiling test; DSX_LR_FORM_SGBM)
-template <bool SSD, bool UNIQ, int LRM, int RING, int NSUM = 0>
+// q = (255 cb) / nm exactly, for cb <= nm (so q <= 255) and nm > 0.  The numerator reaches
+// 255 * 225 * 255^2 = 3,730,809,375 (SSD 15x15) and is formed in 64 bits; the quotient is estimated in
+// fp32 (three roundings and the reciprocal's 1 ulp: an error below 256 * 2^-21, so within one of the
+// quotient) and then settled against the 64-bit products.
+__device__ __forceinline__ uint32_t conf_quot(uint32_t cb, uint32_t nm) {
+    const uint64_t num = 255ull * cb;
+    uint32_t q = (uint32_t)((float)cb * 255.0f * __builtin_amdgcn_rcpf((float)nm));
+    const uint64_t p = (uint64_t)q * nm;
+    if (p > num) --q;
+    else if (num - p >= nm) ++q;
+    return q;
+}
+
+// CONF: the confidence variant (dsx_confidence of dsx.h).  The rival scan runs whatever `uniq` is (these
+// builds take UNIQ = true: with uniq 0 the test never fires, nm >= cb), lane s == 0 forms the peak ratio q
+// into a uint8 LDS row, and the finalising loop stores it and applies q < conf_t after the LR test.
+template <bool SSD, bool UNIQ, int LRM, int RING, int NSUM = 0, bool CONF = false>
 __global__ __launch_bounds__(kVolThreads) void vol_wta(VolArgs a) {
+    static_assert(!CONF || UNIQ, "the confidence variant always scans the rivals");
     // NSUM > 0 (SGM, SSD = true): the u32 costs are the sums of NSUM u16 volumes (one L_r per
     // path direction), loaded as 2 x 16 B per volume and summed when the chunk is processed
     static_assert(NSUM == 0 || SSD, "summed volumes are reduced as u32 costs");
@@ -117,6 +134,11 @@ __global__ __launch_bounds__(kVolThreads) void vol_wta(VolArgs a) {
     uint32_t *bestR = reinterpret_cast<uint32_t *>(rowbase + (size_t)round16(S * 4) + fbytes);
     auto ridx = [&](int xr) __attribute__((always_inline)) { return xr + m + Dp - 1; };
     int16_t *rowB = reinterpret_cast<int16_t *>(rowbase + (size_t)round16(S * 4) + fbytes + (size_t)round16(kvrow(W, Dp) * 4));
+    // confidence row, one byte per pixel of the segment, behind everything else (no other offset moves)
+    uint8_t *rowQ = nullptr;
+    if constexpr (CONF)
+        rowQ = rowbase + (size_t)round16(S * 4) + fbytes +
+               (lr ? (size_t)round16(kvrow(W, Dp) * 4) + (size_t)round16(W * 2) : 0);
     if (lr) {
         for (int i = tid; i < kvrow(W, Dp); i += kVolThreads) bestR[i] = 0xFFFFFFFFu;
         __syncthreads();
@@ -190,6 +212,7 @@ __global__ __launch_bounds__(kVolThreads) void vol_wta(VolArgs a) {
         const uint32_t cb = best >> DB;
         // valid band: A5' [m + D - 1, W - 1 + m]; OpenCV SGBM [max(m + D, 0), W + min(m, 0))
         bool valid = LRM == 2 ? (inb && x >= max(m + D, 0) && x < W + min(m, 0)) : (inb && x >= m + D - 1 && x <= W - 1 + m);
+        [[maybe_unused]] uint32_t qc = 0;
         if (UNIQ) {
             uint32_t nm = 0xFFFFFFFFu;
 #pragma unroll
@@ -198,6 +221,9 @@ __global__ __launch_bounds__(kVolThreads) void vol_wta(VolArgs a) {
                 if ((dd > 1 || dd < -1) && dbase + j < D) nm = umin(nm, slice_cost<SSD>(cur, j));
             }
             nm = group_min(nm, TPP);
+            // peak ratio of the WTA decision alone: 0 outside the band, 255 with no rival at |d - b| > 1
+            // (nm untouched: every real cost lies below the pad), 0 for nm == 0 (then cb == 0: a tie)
+            if constexpr (CONF) qc = !valid ? 0u : nm == 0xFFFFFFFFu ? 255u : nm == 0u ? 0u : 255u - conf_quot(cb, nm);
             if ((uint64_t)nm * (uint64_t)(100 - a.uniq) < (uint64_t)cb * 100u) valid = false;
         }
         if (LRM == 1 && inb) {
@@ -237,6 +263,7 @@ __global__ __launch_bounds__(kVolThreads) void vol_wta(VolArgs a) {
             // the largest d: key (cost << DB) | (dmask - d)
             if (LRM == 2 && valid) atomicMin(&bestR[ridx(x - m - b)], (cb << DB) | (dmask - (uint32_t)b));
             if (a.float_mode == 1) rowF[x - xa] = valid ? pf : (float)(m - 1);
+            if constexpr (CONF) rowQ[x - xa] = (uint8_t)qc;
         }
         if (a.subpix) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront", "local");  // reads before next writes
     };
@@ -287,6 +314,14 @@ __global__ __launch_bounds__(kVolThreads) void vol_wta(VolArgs a) {
             if (!valid) fx = (int16_t)inv;
         }
         const long o = (long)y * W + x;
+        if constexpr (CONF) {
+            const int q = rowQ[x - xa];
+            if (a.out_conf) a.out_conf[o] = (uint8_t)q;
+            if (q < a.conf_t) {
+                valid = false;
+                fx = (int16_t)((m - 1) * 16);
+            }
+        }
         if (a.out_fixed) a.out_fixed[o] = fx;
         if (a.out_float) a.out_float[o] = a.float_mode == 0 ? (float)fx * 0.0625f : (valid ? rowF[x - xa] : (float)(m - 1));
     }
@@ -418,24 +453,25 @@ hipError_t launch_lr_fixup_sgbm(const int16_t *fixed, const uint32_t *keys, int 
 // ---------------------------------------------------------------------------------------
 // scratch (padded slots) + segment results (int32, and f32 for float_mode 1, per pixel of an
 // S-pixel segment) + LR row state (bestR u32 + rowB int16 per pixel of the row)
-static size_t vol_smem(bool ssd, int S, int W, int Dp, bool lr, bool fm1) {
+// confidence variant: + one byte per pixel of the segment
+static size_t vol_smem(bool ssd, int S, int W, int Dp, bool lr, bool fm1, bool conf) {
     return (size_t)kVolScratch * (ssd ? 64 : 32) + (size_t)round16(S * 4) * (fm1 ? 2 : 1) +
-           (lr ? (size_t)round16(kvrow(W, Dp) * 4) + (size_t)round16(W * 2) : 0);
+           (lr ? (size_t)round16(kvrow(W, Dp) * 4) + (size_t)round16(W * 2) : 0) + (conf ? (size_t)round16(S) : 0);
 }
 
-size_t volume_smem_bytes(int TX, bool ssd, int Dp, int TPP, int W) {
+size_t volume_smem_bytes(int TX, bool ssd, int Dp, int TPP, int W, bool conf) {
     (void)TX, (void)TPP;
-    return vol_smem(ssd, W, W, Dp, true, true);  // the largest form (one segment per row, LR, float_mode 1)
+    return vol_smem(ssd, W, W, Dp, true, true, conf);  // the largest form (one segment per row, LR, float_mode 1)
 }
 
-template <bool SSD, bool UNIQ, int LRM, int RING, int NSUM = 0>
+template <bool SSD, bool UNIQ, int LRM, int RING, int NSUM = 0, bool CONF = false>
 static hipError_t launch_vol_ring(const VolArgs &a, hipStream_t st) {
     constexpr bool LR = LRM != 0;
     static bool attr_done[64] = {};
     int dev = 0;
     (void)hipGetDevice(&dev);
     if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void *)vol_wta<SSD, UNIQ, LRM, RING, NSUM>,
+        hipError_t e = hipFuncSetAttribute((const void *)vol_wta<SSD, UNIQ, LRM, RING, NSUM, CONF>,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
         if (dev >= 0 && dev < 64) attr_done[dev] = true;
@@ -449,20 +485,20 @@ static hipError_t launch_vol_ring(const VolArgs &a, hipStream_t st) {
     const int nseg = LR ? 1 : (seg > 1 ? seg : 1);
     const int XC = kVolThreads / (a.Dp / 16);
     const int XSg = ((a.W + nseg - 1) / nseg + XC - 1) / XC * XC;  // as the kernel computes it
-    const size_t smem = vol_smem(SSD, std::min(XSg, a.W), a.W, a.Dp, LR, a.float_mode == 1);
-    hipLaunchKernelGGL((vol_wta<SSD, UNIQ, LRM, RING, NSUM>), dim3(a.H, nseg), dim3(kVolThreads), smem, st, a);
+    const size_t smem = vol_smem(SSD, std::min(XSg, a.W), a.W, a.Dp, LR, a.float_mode == 1, CONF);
+    hipLaunchKernelGGL((vol_wta<SSD, UNIQ, LRM, RING, NSUM, CONF>), dim3(a.H, nseg), dim3(kVolThreads), smem, st, a);
     return hipGetLastError();
 }
 
 // LR form: 0 off, 1 A5' (disp12_max_diff >= 0), 2 OpenCV SGBM (always on, disp12MaxDiff >= 1)
 static int lr_mode(const VolArgs &a) { return a.lr_form == 1 ? 2 : (a.lr >= 0 ? 1 : 0); }
 
-template <bool SSD, bool UNIQ, int RING, int NSUM = 0>
+template <bool SSD, bool UNIQ, int RING, int NSUM = 0, bool CONF = false>
 static hipError_t launch_vol_lr(const VolArgs &a, hipStream_t st) {
     switch (lr_mode(a)) {
-        case 0: return launch_vol_ring<SSD, UNIQ, 0, RING, NSUM>(a, st);
-        case 1: return launch_vol_ring<SSD, UNIQ, 1, RING, NSUM>(a, st);
-        default: return launch_vol_ring<SSD, UNIQ, 2, RING, NSUM>(a, st);
+        case 0: return launch_vol_ring<SSD, UNIQ, 0, RING, NSUM, CONF>(a, st);
+        case 1: return launch_vol_ring<SSD, UNIQ, 1, RING, NSUM, CONF>(a, st);
+        default: return launch_vol_ring<SSD, UNIQ, 2, RING, NSUM, CONF>(a, st);
     }
 }
 
@@ -471,6 +507,7 @@ static hipError_t launch_vol_lr(const VolArgs &a, hipStream_t st) {
 #endif
 template <bool SSD>
 static hipError_t launch_vol_cost(const VolArgs &a, hipStream_t st) {
+    if (a.conf) return launch_vol_lr<SSD, true, 3, 0, true>(a, st);  // one build per LR mode, whatever uniq is
     if (lr_mode(a) == 1 && DSX_K2_RING_LR != 3)
         return a.uniq > 0 ? launch_vol_ring<SSD, true, 1, DSX_K2_RING_LR>(a, st) : launch_vol_ring<SSD, false, 1, DSX_K2_RING_LR>(a, st);
     return a.uniq > 0 ? launch_vol_lr<SSD, true, 3>(a, st) : launch_vol_lr<SSD, false, 3>(a, st);
@@ -481,6 +518,7 @@ static hipError_t launch_vol_cost(const VolArgs &a, hipStream_t st) {
 template <int N>
 static hipError_t launch_vol_sum(const VolArgs &a, hipStream_t st) {
     constexpr int RING = N <= 4 ? 3 : 2;
+    if (a.conf) return launch_vol_lr<true, true, RING, N, true>(a, st);
     return a.uniq > 0 ? launch_vol_lr<true, true, RING, N>(a, st) : launch_vol_lr<true, false, RING, N>(a, st);
 }
 

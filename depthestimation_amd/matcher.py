@@ -86,8 +86,12 @@ class HipBlockMatcher:
                  disp12_max_diff=1, subpixel=True, float_mode="fixed", path="fused", device=0,
                  timing=False, grid_blocks=0, aggregation=None, p1=0, p2=0, prefilter_cap=31,
                  sgbm_post=False, speckle_window_size=50, speckle_range=2, lr_form="bm", in_flight=False,
-                 prefilter_type="none", prefilter_size=9, texture_threshold=0):
-        """``prefilter_type`` 'xsobel' | 'mean' filters both views on the device before the search
+                 prefilter_type="none", prefilter_size=9, texture_threshold=0, confidence_threshold=0):
+        """``confidence_threshold`` t in [0, 255] (0: off) invalidates the pixels whose peak-ratio confidence
+        (depthestimation_amd/confidence.py; ``compute(..., out_confidence=)`` returns the map) is below t,
+        after the LR check.  A matcher with t > 0, and any call that asks for the map, runs the volume path.
+
+        ``prefilter_type`` 'xsobel' | 'mean' filters both views on the device before the search
         (``prefilter_cap`` is its cap, ``prefilter_size`` the window of 'mean'); ``texture_threshold`` > 0
         then invalidates the pixels whose filtered block has less texture (depthestimation_amd/prefilter.py
         restates both).  The defaults ('none', 0) run no extra kernel."""
@@ -99,6 +103,7 @@ class HipBlockMatcher:
         _dsx.check_params(self._params)  # validates on the host, no device needed
         self._prefilter = _dsx.make_prefilter(prefilter_type, prefilter_size, prefilter_cap, texture_threshold)
         _dsx.check_prefilter(self._params, self._prefilter)
+        self._confidence = _dsx.make_confidence(confidence_threshold)
         self._h = None
         self._cfg = dict(min_disp=min_disp, num_disp=num_disp, block_size=block_size, cost=cost,
                          uniqueness_ratio=uniqueness_ratio, disp12_max_diff=disp12_max_diff,
@@ -107,15 +112,16 @@ class HipBlockMatcher:
                          prefilter_cap=prefilter_cap, sgbm_post=sgbm_post,
                          speckle_window_size=speckle_window_size, speckle_range=speckle_range, lr_form=lr_form,
                          in_flight=in_flight, prefilter_type=prefilter_type, prefilter_size=prefilter_size,
-                         texture_threshold=texture_threshold)
+                         texture_threshold=texture_threshold, confidence_threshold=confidence_threshold)
 
+    _CONFIDENCE_DEFAULTS = {"confidence_threshold": 0}
     _PREFILTER_DEFAULTS = {"prefilter_type": "none", "prefilter_size": 9, "texture_threshold": 0}
     _PREFILTER_KEYS = tuple(_PREFILTER_DEFAULTS)
 
     @classmethod
     def _split_cfg(cls, cfg):
         """(dsx_params, dsx_prefilter) of a configuration dict."""
-        base = {k: v for k, v in cfg.items() if k not in cls._PREFILTER_KEYS}
+        base = {k: v for k, v in cfg.items() if k not in cls._PREFILTER_KEYS and k not in cls._CONFIDENCE_DEFAULTS}
         params = _dsx.make_params(**base)
         pre = _dsx.make_prefilter(cfg["prefilter_type"], cfg["prefilter_size"], cfg["prefilter_cap"],
                                   cfg["texture_threshold"])
@@ -135,6 +141,11 @@ class HipBlockMatcher:
                 if rc != _dsx.DSX_OK:
                     L.dsx_destroy(h)
                     _dsx.check(rc, "dsx_set_prefilter")
+            if self._confidence.threshold:
+                rc = L.dsx_set_confidence(h, ctypes.byref(self._confidence))
+                if rc != _dsx.DSX_OK:
+                    L.dsx_destroy(h)
+                    _dsx.check(rc, "dsx_set_confidence")
             self._h = h
         return self._h
 
@@ -153,8 +164,10 @@ class HipBlockMatcher:
     def params(self) -> dict:
         """The constructor keywords of this matcher.  The prefilter keys are reported once any of them
         is off its default ('none', 9, 0), so a matcher without a prefilter reports the set it always
-        did; ``prefilter_params`` reports them always."""
+        did; ``prefilter_params`` reports them always.  ``confidence_threshold`` follows the same rule."""
         cfg = dict(self._cfg)
+        if cfg["confidence_threshold"] == self._CONFIDENCE_DEFAULTS["confidence_threshold"]:
+            del cfg["confidence_threshold"]
         if all(cfg[k] == d for k, d in self._PREFILTER_DEFAULTS.items()):
             for k in self._PREFILTER_DEFAULTS:
                 del cfg[k]
@@ -181,6 +194,7 @@ class HipBlockMatcher:
             raise ValueError(f"set_params: {e}") from e
         _dsx.check_params(params)
         _dsx.check_prefilter(params, pre)
+        conf = _dsx.make_confidence(cfg["confidence_threshold"])
         if self._h is not None:
             L = _dsx.lib()
 
@@ -199,7 +213,11 @@ class HipBlockMatcher:
             # comes on or changes arrives after the parameters it was checked with
             for step in ((set_f, set_p) if pre.type == _dsx.PREFILTER["none"] else (set_p, set_f)):
                 step()
-        self._params, self._prefilter, self._cfg = params, pre, cfg
+            # the confidence set was validated above and depends on no other parameter
+            rc = L.dsx_set_confidence(self._h, ctypes.byref(conf))
+            if rc != _dsx.DSX_OK:
+                raise ValueError(f"dsx_set_confidence: {_dsx.last_error() or 'error ' + str(rc)}")
+        self._params, self._prefilter, self._confidence, self._cfg = params, pre, conf, cfg
 
     # -- cv2.StereoMatcher-style getters (cv2 names used by depthlib docs) --------------------
     def getMinDisparity(self):
@@ -227,8 +245,9 @@ class HipBlockMatcher:
             a = np.ascontiguousarray(a)
         return a
 
-    def compute(self, left, right, out_float=None):
-        """cv2 StereoMatcher.compute contract (stereo_core.py:231): int16 H x W, x16."""
+    def compute(self, left, right, out_float=None, out_confidence=None):
+        """cv2 StereoMatcher.compute contract (stereo_core.py:231): int16 H x W, x16.  ``out_confidence``:
+        a contiguous uint8 H x W array that takes the peak-ratio confidence map (dsx_compute_conf_host)."""
         L = self._as_gray(left, "left")
         R = self._as_gray(right, "right")
         if L.shape != R.shape:
@@ -243,14 +262,24 @@ class HipBlockMatcher:
             if out_float.shape != (H, W) or out_float.dtype != np.float32 or not out_float.flags.c_contiguous:
                 raise ValueError("out_float must be a contiguous float32 H x W array")
             fptr = out_float.ctypes.data
+        if out_confidence is not None:
+            if not isinstance(out_confidence, np.ndarray) or out_confidence.shape != (H, W) or \
+                    out_confidence.dtype != np.uint8 or not out_confidence.flags.c_contiguous:
+                raise ValueError("out_confidence must be a contiguous uint8 H x W array")
+            rc = _dsx.lib().dsx_compute_conf_host(self._handle(), L.ctypes.data, R.ctypes.data, H, W, L.strides[0],
+                                                  out.ctypes.data, fptr, out_confidence.ctypes.data)
+            _dsx.check(rc, "dsx_compute_conf_host")
+            return out
         rc = _dsx.lib().dsx_compute_host(self._handle(), L.ctypes.data, R.ctypes.data, H, W, L.strides[0],
                                          out.ctypes.data, fptr)
         _dsx.check(rc, "dsx_compute_host")
         return out
 
-    def compute_device(self, left, right, out_fixed=None, out_float=None, stream=None, stride=None):
+    def compute_device(self, left, right, out_fixed=None, out_float=None, stream=None, stride=None,
+                       out_confidence=None):
         """Async device compute. ``left``/``right``: uint8 CUDA/HIP tensors (H x W, unit column
-        stride) or (ptr, H, W) tuples.  Outputs are caller-owned contiguous device buffers."""
+        stride) or (ptr, H, W) tuples.  Outputs are caller-owned contiguous device buffers;
+        ``out_confidence`` (uint8 H x W) takes the peak-ratio confidence map (dsx_compute_conf_device)."""
         if isinstance(left, tuple):
             lp, H, W = left
             rp = right[0] if isinstance(right, tuple) else _ptr(right)
@@ -264,16 +293,22 @@ class HipBlockMatcher:
             _check_inputs_on(self.device, left, right)
             H, W = left.shape
             lp, rp, st = left.data_ptr(), right.data_ptr(), ls[0]
-        if out_fixed is None and out_float is None:
+        if out_fixed is None and out_float is None and out_confidence is None:
             raise ValueError("at least one of out_fixed / out_float is required")
         _check_out(out_fixed, (H, W), "torch.int16", self.device, "out_fixed")
         _check_out(out_float, (H, W), "torch.float32", self.device, "out_float")
+        _check_out(out_confidence, (H, W), "torch.uint8", self.device, "out_confidence")
         if stream is None:
             sptr = None
         elif isinstance(stream, int):
             sptr = stream
         else:
             sptr = stream.cuda_stream
+        if out_confidence is not None:
+            rc = _dsx.lib().dsx_compute_conf_device(self._handle(), lp, rp, H, W, st, _ptr(out_fixed), _ptr(out_float),
+                                                    _ptr(out_confidence), sptr)
+            _dsx.check(rc, "dsx_compute_conf_device")
+            return
         rc = _dsx.lib().dsx_compute_device(self._handle(), lp, rp, H, W, st, _ptr(out_fixed), _ptr(out_float), sptr)
         _dsx.check(rc, "dsx_compute_device")
 

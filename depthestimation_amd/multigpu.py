@@ -220,7 +220,10 @@ class HostPipeline:
     Buffer lifetime: a pinned tensor input is read by an asynchronous copy on the frame's stream,
     so the caller must not modify it until that frame's result has been returned (by ``push``,
     ``poll`` or ``drain_all``); a decoder reusing a pinned ring needs a ring at least ``depth + 1``
-    frames deep.  Numpy inputs are copied into the slot inside ``push`` and may be reused at once."""
+    frames deep.  Numpy inputs are copied into the slot inside ``push`` and may be reused at once.
+
+    ``confidence_threshold`` among ``matcher_kw`` is honoured (the frames then run the volume path); the
+    pipeline returns no confidence map."""
 
     def __init__(self, device: int, depth: int = 3, streams: int = 2, copy: bool = True, **matcher_kw):
         import torch
@@ -338,7 +341,10 @@ class DepthPipeline:
     depth maps (numpy copies, None when focal length / baseline are unset - what the reference's
     generator yields, StereoDepthEstimatorVideo.py:101-103).  ``input_scale``: the pinned slots and the
     uploads carry full-size frames and the input downscale (``input.resize_area_device``) runs on the
-    frame's stream, equal bit for bit to pushing ``resize_area`` of the frames."""
+    frame's stream, equal bit for bit to pushing ``resize_area`` of the frames.
+
+    The core's 'confidence_threshold' is honoured; the pipeline returns no confidence map (with
+    'confidence': True each slot's core keeps its last frame's map, which no result carries)."""
 
     def __init__(self, core, device: int, depth: int = 3, streams: int = 2, input_scale=None):
         import copy
@@ -505,7 +511,10 @@ class BandedStereo:
     to the image, r = block_size // 2 (plus the reach of a prefilter or a census window).  Every term of the A5' contract is row-local except the
     vertical window, which the halo supplies, and the image's own top / bottom clamp coincides
     with the sub-image's, so the stitched map equals the single-device result bit for bit.
-    ``devices`` may repeat a device (several bands on one GPU, e.g. for testing)."""
+    ``devices`` may repeat a device (several bands on one GPU, e.g. for testing).
+    ``confidence_threshold`` is honoured band by band (the peak ratio is a per-pixel function of the block
+    costs, which the halo makes whole; not under SGM, whose vertical paths cross the bands); no map is
+    returned."""
 
     def __init__(self, devices: Optional[Sequence[int]] = None, **matcher_kw):
         n = _dsx.device_count()

@@ -51,6 +51,15 @@ Keys added to ``sgbm_params`` (accepted by ``configure_sgbm`` like the reference
                                        launch, fast enough for video.  'refine_radius' 1..7 (5),
                                        'refine_sigma' 1..64 grey levels (8).  Ignored in fast mode, as
                                        'hole_filling' is)
+  'confidence': bool                  (False.  True: ``_process_pair`` and ``process_pair_device`` also keep
+                                       the matcher's peak-ratio confidence map (confidence.py; uint8, 255 =
+                                       no rival, 0 = a tie or outside the valid band), cropped like the
+                                       disparity, in ``confidence_map`` - a numpy array on the host, a
+                                       tensor on the device.  The map comes from the volume path's K2, so a
+                                       SAD / SSD core pays that path for it; return values are unchanged)
+  'confidence_threshold': int         (0 = off; t in 1..255: pixels of confidence below t become invalid
+                                       after the LR check, before the texture mask and 'sgbm_post' - holes
+                                       for the fillers and 'refine' to close from trusted neighbours)
 Keys of the reference that have no block-matching meaning are kept, validated and reported
 but do not change the result: 'prefilter_cap' unless 'cost' is 'bt' or a prefilter is set, 'speckle_window_size' /
 'speckle_range' unless 'sgbm_post' is set, and 'sgbm_mode' / P1 / P2 while 'aggregation' is 'none'
@@ -155,7 +164,10 @@ class StereoCore:
             'refine_radius': 5,
             'refine_sigma': 8,
             'refine_fill': True,
+            'confidence': False,
+            'confidence_threshold': 0,
         }
+        self.confidence_map = None
         self._build_sgbm()
         self.disparity_map = None
         self.depth_map = None
@@ -176,6 +188,12 @@ class StereoCore:
             raise ValueError("Invalid parameter value for 'refine_radius': expected an integer in [1, 7]")
         if isinstance(sg, bool) or int(sg) != sg or not 1 <= int(sg) <= 64:
             raise ValueError("Invalid parameter value for 'refine_sigma': expected an integer in [1, 64]")
+        if not isinstance(p.get('confidence', False), (bool, np.bool_)):
+            raise ValueError("Invalid parameter value for 'confidence': expected a bool")
+        t = p.get('confidence_threshold', 0)
+        if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, float, np.integer, np.floating)) or \
+                int(t) != t or not 0 <= int(t) <= 255:
+            raise ValueError("Invalid parameter value for 'confidence_threshold': expected an integer in [0, 255]")
         self.P1 = 8 * p['block_size'] ** 2
         self.P2 = 32 * p['block_size'] ** 2
         self.mode = p.get('sgbm_mode', 'sgbm_3way') if p.get('sgbm_mode') in _SGBM_MODES else 'sgbm_3way'
@@ -200,6 +218,7 @@ class StereoCore:
             prefilter_type=p.get('prefilter_type', 'none'),
             prefilter_size=p.get('prefilter_size', 9),
             texture_threshold=p.get('texture_threshold', 0),
+            confidence_threshold=int(t),
         )
         if old is not None:
             old.close()
@@ -248,7 +267,15 @@ class StereoCore:
     def _process_pair(self, left_img: np.ndarray, right_img: np.ndarray) -> Tuple[np.ndarray, Optional[np.ndarray]]:
         """stereo_core.py:162-200: disparity -> crop [:, num_disp:] -> median (fast) or
         postprocess -> depth when focal length and baseline are set."""
-        disparity_px = self.compute_disparity(left_img, right_img)
+        if self.sgbm_params.get('confidence', False) and 'compute_disparity' not in self.__dict__:
+            if self.sgbm is None:
+                self._build_sgbm()
+            conf = np.empty(np.asarray(left_img).shape[:2], np.uint8)
+            disparity_px = self.sgbm.compute(left_img, right_img, out_confidence=conf).astype(np.float32) / 16.0
+            self.confidence_map = conf[:, self.sgbm_params['num_disp']:]
+        else:
+            disparity_px = self.compute_disparity(left_img, right_img)
+            self.confidence_map = None
         disparity_px = disparity_px[:, self.sgbm_params['num_disp']:]
         refine = self._refine_kwargs()
         if refine['refine'] != 'none' and not self.fast_mode:
@@ -350,7 +377,9 @@ class StereoCore:
         fill = bool(p.get('hole_filling', False)) and not self.fast_mode
         method = p.get('fill_method', 'inpaint')
         timed = fill and method == 'inpaint'  # only Telea's persistent launch can time out
-        if 'compute_disparity_device' not in self.__dict__ and self.sgbm is not None and \
+        want_conf = bool(p.get('confidence', False)) and 'compute_disparity_device' not in self.__dict__
+        self.confidence_map = None
+        if not want_conf and 'compute_disparity_device' not in self.__dict__ and self.sgbm is not None and \
                 getattr(self.sgbm, 'process_pair_device', None) is not None and \
                 getattr(self.sgbm, 'params', {}).get('float_mode', 'fixed') == 'fixed':
             # one C-ABI call per frame (dsx_process_pair_device): the handle owns the float map and
@@ -361,7 +390,17 @@ class StereoCore:
                 max_diff=1.0, apply_outlier_removal=True, outlier_threshold=2.5, outlier_kernel=5,
                 fill_radius=3 if p.get('hole_filling', False) else 0, focal_length=f, baseline=B, doffs=doffs,
                 eps=eps, max_depth=max_depth, stream=stream, fill_method=method, **self._refine_kwargs())
-        disp = self.compute_disparity_device(left, right, stream=stream)
+        if want_conf:
+            # the map comes with the matcher call: the two-step route (compute_device, then the post-processing)
+            import torch
+            if self.sgbm is None:
+                self._build_sgbm()
+            disp = torch.empty(left.shape, dtype=torch.float32, device=left.device)
+            conf = torch.empty(left.shape, dtype=torch.uint8, device=left.device)
+            self.sgbm.compute_device(left, right, out_float=disp, stream=stream, out_confidence=conf)
+            self.confidence_map = conf[:, p['num_disp']:]
+        else:
+            disp = self.compute_disparity_device(left, right, stream=stream)
         self._fill_check = None
         if self.fast_mode:
             return postprocess_fast_device(disp, p['num_disp'], f, B, doffs, eps, max_depth, stream=stream)
@@ -414,6 +453,8 @@ class StereoCore:
             self.right_rectified = _HostView(self.right_rectified)
             self.disparity_map = d.cpu().numpy()
             self.depth_map = None if z is None else z.cpu().numpy()
+            if self.confidence_map is not None:  # host arrays in, host arrays out
+                self.confidence_map = self.confidence_map.cpu().numpy()
             self.check_fill_status()  # the copies above waited for the march: a timed-out fill raises
             return self.disparity_map, self.depth_map
         self.left_rectified, self.right_rectified = self._prepare_rectified(left_source, right_source)

@@ -32,7 +32,10 @@
 extern "C" {
 #endif
 
-#define DSX_VERSION 106 /* additive since 1.0.6 (layouts unchanged): dsx_refine, dsx_default_refine, dsx_check_refine,
+#define DSX_VERSION 106 /* additive since 1.0.6 (layouts unchanged): dsx_confidence, dsx_default_confidence,
+                           dsx_check_confidence, dsx_set_confidence, dsx_compute_conf_device, dsx_compute_conf_host
+                           (matcher confidence map + threshold);
+                           dsx_refine, dsx_default_refine, dsx_check_refine,
                            dsx_wmedian_weights, dsx_wmedian_device, dsx_postprocess_refine_device,
                            dsx_process_pair_refine_device (image-guided weighted median);
                            DSX_COST_CENSUS*, dsx_census_device, dsx_resize_area_*, dsx_fill_nearest_*,
@@ -213,6 +216,52 @@ int dsx_texture_sum_device(const void *d_pref, int32_t H, int32_t W, int64_t str
  * `cost` (DSX_COST_CENSUS9X7: 62 bits, DSX_COST_CENSUS5X5: 24 bits; the upper bits 0). */
 int dsx_census_device(const void *d_img, int32_t H, int32_t W, int64_t stride_bytes, int32_t cost, void *d_out_u64,
                       void *hip_stream);
+
+/* Matcher confidence map and confidence threshold.  An addition of this build (as the prefilter and the
+ * census costs are): parity with nothing outside this repository is claimed.
+ * Let C(x, y, d), d in [0, D), be the costs the epilogue decides on (block costs of any `cost`, or SGM path
+ * sums), b the lowest-d argmin, cb = C(b), and nm the minimum of C(d) over the real disparities with
+ * |d - b| > 1 (the set the uniqueness test scans).  DSX_CONF_PEAK_RATIO is the uint8
+ *   q = 255                        if that set is empty (D <= 2, or D = 3 with b = 1),
+ *   q = 0                          if nm == 0 (then cb == 0: a perfect tie),
+ *   q = 255 - (255 * cb) / nm      otherwise (integer division; cb <= nm, so q is in [0, 255]),
+ *   q = 0                          outside the handle's valid band (lr_form BM: [m + D - 1, W - 1 + m];
+ *                                  SGBM: [max(m + D, 0), W + min(m, 0))).
+ * q describes the WTA decision alone: it does not depend on the uniqueness, LR, texture, sub-pixel or
+ * sgbm_post outcomes.  Every in-band pixel that uniqueness_ratio u rejects has q <= 255 - (255 (100 - u)) / 100.
+ *   threshold t in [0, 255], 0 = off: a pixel with q < t gets the invalid value ((min_disp - 1) * 16;
+ *       min_disp - 1 in the float map) after the LR check of either form - it still takes part in the
+ *       right-view winners and, for DSX_LR_FORM_SGBM, still offers its key - and before the texture mask
+ *       and the sgbm_post tail.
+ * The map comes from K2 of the volume path: a call that is handed a confidence output, and every call of a
+ * handle whose threshold is > 0, runs the volume path also on a handle that otherwise runs the fused pass
+ * (same disparities; the volume buffer is allocated on first need and such a call uses handle scratch).
+ * The handle's other calls stay fused.  dsx_right_map_device is unaffected.  dsx_compute_device,
+ * dsx_compute_batch_device and dsx_process_pair*_device honour the threshold and return no map. */
+#define DSX_CONF_PEAK_RATIO 1
+typedef struct dsx_confidence {
+    int32_t type;      /* DSX_CONF_PEAK_RATIO */
+    int32_t threshold; /* 0 (off) .. 255      */
+    int32_t reserved[6];
+} dsx_confidence;
+
+/* PEAK_RATIO, threshold 0 */
+void dsx_default_confidence(dsx_confidence *c);
+
+/* Validate a confidence set, alone (p NULL) or against matcher parameters (no handle, no device). */
+int dsx_check_confidence(const dsx_params *p, const dsx_confidence *c);
+
+/* Set the handle's confidence set (NULL = default); on error the handle keeps its old set. */
+int dsx_set_confidence(dsx_handle *h, const dsx_confidence *c);
+
+/* dsx_compute_device / dsx_compute_host with the confidence map: d_out_conf / out_conf uint8 H x W,
+ * contiguous.  With it NULL these are exactly dsx_compute_device / dsx_compute_host; otherwise at least one
+ * of the three outputs is required (the host call needs no out_fixed then).  Argument errors are reported
+ * before any HIP call. */
+int dsx_compute_conf_device(dsx_handle *h, const void *dL, const void *dR, int32_t H, int32_t W, int64_t stride_bytes,
+                            void *d_out_fixed, void *d_out_float, void *d_out_conf, void *hip_stream);
+int dsx_compute_conf_host(dsx_handle *h, const uint8_t *L, const uint8_t *R, int32_t H, int32_t W, int64_t stride_bytes,
+                          int16_t *out_fixed, float *out_float, uint8_t *out_conf);
 
 /* Synchronous host-buffer compute (replaces matcher.compute, stereo_core.py:231).
  * L, R: uint8 H x W with row stride `stride_bytes` (>= W).  out_fixed: int16 H x W

@@ -25,6 +25,11 @@ class _Prefilter(ctypes.Structure):
         ("reserved", ctypes.c_int32 * 4)]
 
 
+class _Confidence(ctypes.Structure):
+    # dsx_confidence (include/dsx.h): type DSX_CONF_PEAK_RATIO = 1, threshold 0..255
+    _fields_ = [("type", ctypes.c_int32), ("threshold", ctypes.c_int32), ("reserved", ctypes.c_int32 * 6)]
+
+
 # preFilterType names -> DSX_PREFILTER_* (this build's own arithmetic, see include/dsx.h)
 PREFILTERS = {None: 0, "none": 0, "xsobel": 1, "mean": 2}
 
@@ -44,6 +49,8 @@ _lib.dsx_compute_host.argtypes = [_vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32,
 _lib.dsx_destroy.argtypes = [_vp]
 _lib.dsx_last_error.restype = ctypes.c_char_p
 _lib.dsx_set_prefilter.argtypes = [_vp, ctypes.POINTER(_Prefilter)]
+_lib.dsx_set_confidence.argtypes = [_vp, ctypes.POINTER(_Confidence)]
+_lib.dsx_compute_conf_host.argtypes = [_vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _vp, _vp, _vp]
 
 
 def make_params(minDisparity=0, numDisparities=128, blockSize=5, disp12MaxDiff=1, uniquenessRatio=10,
@@ -68,11 +75,17 @@ class DsxStereoMatcher:
 
     def __init__(self, minDisparity=0, numDisparities=128, blockSize=5, disp12MaxDiff=1,
                  uniquenessRatio=10, cost=0, device=0, sgbm_mode=None, P1=0, P2=0, preFilterCap=31,
-                 preFilterType=None, preFilterSize=9, textureThreshold=0, **_sgbm_only_keys):
+                 preFilterType=None, preFilterSize=9, textureThreshold=0, confidenceThreshold=0,
+                 **_sgbm_only_keys):
         # preFilterType 'xsobel' | 'mean' (cv2.StereoBM's keyword names): both views are filtered on the
         # device before the SAD / SSD search, cap preFilterCap; textureThreshold > 0 needs one
         p = make_params(minDisparity, numDisparities, blockSize, disp12MaxDiff, uniquenessRatio, cost,
                         sgbm_mode, P1, P2, preFilterCap)
+        # confidenceThreshold t in 1..255: pixels whose peak-ratio confidence is below t become invalid
+        # (this build's addition; the matcher then runs its volume path)
+        if isinstance(confidenceThreshold, bool) or int(confidenceThreshold) != confidenceThreshold or \
+                not 0 <= confidenceThreshold <= 255:
+            raise ValueError("confidenceThreshold must be an integer in [0, 255]")
         self._h = _vp()
         if _lib.dsx_create(device, ctypes.byref(p), ctypes.byref(self._h)) != 0:
             self._h = None
@@ -84,6 +97,25 @@ class DsxStereoMatcher:
                 _lib.dsx_destroy(self._h)
                 self._h = None
                 raise ValueError(msg)
+        if confidenceThreshold:
+            c = _Confidence(1, int(confidenceThreshold))
+            if _lib.dsx_set_confidence(self._h, ctypes.byref(c)) != 0:
+                msg = _lib.dsx_last_error().decode()
+                _lib.dsx_destroy(self._h)
+                self._h = None
+                raise ValueError(msg)
+
+    def compute_with_confidence(self, left, right):
+        """(int16 x16 disparity, uint8 peak-ratio confidence: 255 = no rival, 0 = a tie or outside the band)."""
+        L = np.ascontiguousarray(left, np.uint8)
+        R = np.ascontiguousarray(right, np.uint8)
+        if L.shape != R.shape or L.ndim != 2:
+            raise ValueError("left/right must be uint8 H x W of the same size")
+        out, conf = np.empty(L.shape, np.int16), np.empty(L.shape, np.uint8)
+        if _lib.dsx_compute_conf_host(self._h, L.ctypes.data, R.ctypes.data, L.shape[0], L.shape[1],
+                                      L.strides[0], out.ctypes.data, None, conf.ctypes.data) != 0:
+            raise RuntimeError(_lib.dsx_last_error().decode())
+        return out, conf
 
     def compute(self, left, right):
         L = np.ascontiguousarray(left, np.uint8)

@@ -35,6 +35,9 @@ def main():
     ap.add_argument("--configs", nargs="+", default=["c4", "c2"])
     ap.add_argument("--modes", nargs="+", default=list(MODES))
     ap.add_argument("--runs", type=int, default=30)
+    ap.add_argument("--confidence", action="store_true",
+                    help="hand every call a confidence output (K2's confidence variant; 'bm' then runs the volume path)")
+    ap.add_argument("--confidence-threshold", type=int, default=0)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     for c in args.configs:
@@ -43,38 +46,42 @@ def main():
         L, R, _ = stereo_pair(H, W, 0, D, seed=1)
         Ld, Rd = torch.from_numpy(L).to(dev), torch.from_numpy(R).to(dev)
         out = torch.empty((H, W), dtype=torch.int16, device=dev)
+        ckw = dict(out_confidence=torch.empty((H, W), dtype=torch.uint8, device=dev)) if args.confidence else {}
         for name in args.modes:
             kw = dict(num_disp=D, block_size=bs, uniqueness_ratio=10, disp12_max_diff=1, p1=8 * bs * bs,
                       p2=32 * bs * bs)
             kw.update(MODES[name])
+            if args.confidence_threshold:
+                kw["confidence_threshold"] = args.confidence_threshold
             if kw.get("cost", "sad") == "sad" and name == "bm":
                 kw["cost"] = cfg["cost"]
             m = HipBlockMatcher(**kw)
             s = torch.cuda.Stream(dev)
             for _ in range(5):
-                m.compute_device(Ld, Rd, out_fixed=out, stream=s)
+                m.compute_device(Ld, Rd, out_fixed=out, stream=s, **ckw)
             s.synchronize()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(s)
             for _ in range(args.runs):
-                m.compute_device(Ld, Rd, out_fixed=out, stream=s)
+                m.compute_device(Ld, Rd, out_fixed=out, stream=s, **ckw)
             e1.record(s)
             e1.synchronize()
             ms = e0.elapsed_time(e1) / args.runs
             m.close()
             mt = HipBlockMatcher(timing=True, **kw)
             for _ in range(3):
-                mt.compute_device(Ld, Rd, out_fixed=out, stream=s)
+                mt.compute_device(Ld, Rd, out_fixed=out, stream=s, **ckw)
             s.synchronize()
             mt.reset_times()
             for _ in range(10):
-                mt.compute_device(Ld, Rd, out_fixed=out, stream=s)
+                mt.compute_device(Ld, Rd, out_fixed=out, stream=s, **ckw)
             s.synchronize()
             kt = {k: round(v[0], 4) for k, v in mt.kernel_times().items()}
             mt.close()
             print(json.dumps({"config": c, "mode": name, "H": H, "W": W, "D": D, "block": bs, "ms": round(ms, 4),
                               "Mpix_s": round(H * W / ms / 1e3, 1), "kernels_ms": kt,
-                              "block_run": kw["block_size"]}), flush=True)
+                              "block_run": kw["block_size"], "confidence": bool(args.confidence),
+                              "confidence_threshold": args.confidence_threshold}), flush=True)
 
 
 if __name__ == "__main__":
