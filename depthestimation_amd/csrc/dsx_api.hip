@@ -11,6 +11,7 @@
 
 #include "../../include/dsx.h"
 #include "dsx_internal.h"
+#include "dsx_plan.h"
 
 extern char **environ;  // the DSX_* tuning variables: dsx_env()
 
@@ -35,68 +36,27 @@ int fail(int code, const std::string &msg) {
                         std::string(#expr) + ": " + hipGetErrorString(e_));                 \
     } while (0)
 
-int bits_for(int n) {  // smallest b with (1 << b) >= n
-    int b = 0;
-    while ((1 << b) < n) ++b;
-    return b < 1 ? 1 : b;
+using namespace dsx;  // the pure decisions of dsx_plan.h
+
+bool env_flag(const char *name) {
+    const char *e = getenv(name);
+    return e && *e == '1';
 }
 
-// bm2 geometry: SAD lanes own disparity pairs (Dp = 128 * nw, nw in {1,2,4}); SSD lanes own
-// one disparity (Dp = 64 * nw, nw in {1,2,4,8}).  K2 (vol_wta) reuses Dp with 32-d slices.
-// SAD with D <= 64 on the fused path takes the SSD layout with u32 |.| sums (BM_SAD1, Dp = 64): the
-// pair layout would spend half of every wave on padding disparities.  DSX_NO_SAD1=1 disables it.
 bool pick_geometry(const dsx_params &p, dsx::Geometry &g) {
-    const int D = p.num_disp, cost = p.cost;
-    static const bool no_sad1 = [] {
-        const char *e = getenv("DSX_NO_SAD1");
-        return e && *e == '1';
-    }();
-    const bool sad1 = !no_sad1 && cost == DSX_COST_SAD && D <= 64 && p.path == DSX_PATH_FUSED &&
-                      p.aggregation == DSX_AGG_NONE;
-    const bool lane1 = cost == DSX_COST_SSD || sad1;  // one disparity per lane
-    g.kind = cost == DSX_COST_SSD ? dsx::BM_SSD : (sad1 ? dsx::BM_SAD1 : dsx::BM_SAD);
-    const int unit = lane1 ? 64 : 128;
-    const int maxnw = lane1 ? 8 : 4;
-    int nw = 1;
-    while (nw * unit < D) nw *= 2;
-    if (nw > maxnw) return false;
-    g.NW = nw;
-    g.Dp = nw * unit;
-    g.TX = 32;
-    g.TPP = g.Dp / 32;
-    g.DB = bits_for(g.Dp);
-    return true;
+    static const bool no_sad1 = env_flag("DSX_NO_SAD1");
+    return dsx::pick_geometry(p, no_sad1, g);
 }
 
-// SGM path sets by mode (oracle/sgm.py DIRECTIONS order)
-const int kSgmDirs[8][2] = {{1, 0}, {-1, 0}, {0, 1}, {0, -1}, {1, 1}, {-1, 1}, {1, -1}, {-1, -1}};
-int sgm_set(int mode, const int **set) {
-    static const int set3[] = {0, 1, 2}, set4[] = {0, 1, 2, 3}, set5[] = {0, 1, 2, 4, 5}, set8[] = {0, 1, 2, 3, 4, 5, 6, 7};
-    switch (mode) {
-        case DSX_AGG_HH4: *set = set4; return 4;
-        case DSX_AGG_SGBM: *set = set5; return 5;
-        case DSX_AGG_HH: *set = set8; return 8;
-        default: *set = set3; return 3;
-    }
-}
-
-int bt_ftzero(const dsx_params &p) { return (p.prefilter_cap > 15 ? p.prefilter_cap : 15) | 1; }
-
-bool is_census(int cost) { return cost == DSX_COST_CENSUS9X7 || cost == DSX_COST_CENSUS5X5; }
-// costs that exist only as a volume (no fused pass, no right-view pass): BT and census
-bool volume_only(int cost) { return cost == DSX_COST_BT || is_census(cost); }
-
-uint64_t max_cost(const dsx_params &p) {
-    const uint64_t n = (uint64_t)p.block_size * p.block_size;
-    if (is_census(p.cost)) return n * (p.cost == DSX_COST_CENSUS9X7 ? 62ull : 24ull);  // Hamming bits per pixel
-    if (p.cost == DSX_COST_BT) return n * (uint64_t)(2 * bt_ftzero(p) + 63);  // oracle/bt_cost.py max_cost_bt
-    return n * (p.cost == DSX_COST_SSD ? 255ull * 255ull : 255ull);
+// odd and in [1, 15]: the matcher's block and dsx_texture_sum_device's
+int check_block_size(int bs) {
+    if (bs < 1 || bs > 15 || (bs & 1) == 0) return fail(DSX_EINVAL, "block_size must be odd and in [1, 15]");
+    return DSX_OK;
 }
 
 int check(const dsx_params *p) {
     if (!p) return fail(DSX_EINVAL, "params is NULL");
-    if (p->block_size < 1 || p->block_size > 15 || (p->block_size & 1) == 0)
-        return fail(DSX_EINVAL, "block_size must be odd and in [1, 15]");
+    if (int rc = check_block_size(p->block_size)) return rc;
     if (p->num_disp < 1 || p->num_disp > 512) return fail(DSX_EINVAL, "num_disp must be in [1, 512]");
     if (p->cost != DSX_COST_SAD && p->cost != DSX_COST_SSD && p->cost != DSX_COST_BT && !is_census(p->cost))
         return fail(DSX_EINVAL, "cost must be SAD (0), SSD (1), BT (2), CENSUS9X7 (3) or CENSUS5X5 (4)");
@@ -168,16 +128,33 @@ int check_confidence(const dsx_params *p, const dsx_confidence *c) {
     return DSX_OK;
 }
 
-// The geometry a handle's volume-path launches use: the fused handle's own, except BM_SAD1 (see dsx_handle.gv).
-void pick_volume_geometry(const dsx_params &p, dsx::Geometry &g) {
-    dsx_params q = p;
-    q.path = DSX_PATH_VOLUME;
-    pick_geometry(q, g);
-}
-
 struct TimedLaunch {
     int kernel;
     hipEvent_t a, b;
+};
+
+// One cached device allocation of a handle: the pointer and the bytes it holds (0: not allocated).
+struct DevBuf {
+    void *ptr = nullptr;
+    size_t held = 0;
+    template <class T>
+    T *as() const { return static_cast<T *>(ptr); }
+    // Grows to at least `need` bytes (it may stay larger; the contents are scratch and are not kept).
+    // hipFree waits for the device, so no earlier launch still uses the old block.  *fresh: it reallocated.
+    int grow(size_t need, bool *fresh = nullptr) {
+        if (fresh) *fresh = false;
+        if (held >= need) return DSX_OK;
+        release();
+        DSX_HIP(hipMalloc(&ptr, need));
+        held = need;
+        if (fresh) *fresh = true;
+        return DSX_OK;
+    }
+    void release() {
+        (void)hipFree(ptr);
+        ptr = nullptr;
+        held = 0;
+    }
 };
 
 }  // namespace
@@ -194,7 +171,7 @@ struct dsx_handle {
     hipStream_t stream = nullptr;  // for dsx_compute_host
     // buffer cache keyed by (H, W, geometry); single entry like RectificationCache (rectify.py:49-50)
     int cH = 0, cW = 0, cDp = 0, cCostBytes = 0;
-    int lrFrames = 0;  // frames the LR buffers hold
+    int lrFrames = 0;  // frames the LR buffers hold: the stride between the two key halves
     int lrParity = 0;  // which half of lrKeys the next frame's left pass fills
     int lrDirty[2] = {0, 0};  // frames of each half holding keys that were not reset yet
     // Handle-owned scratch (LR keys / left winners, cost volume, BT records, SGM sums, the
@@ -204,41 +181,24 @@ struct dsx_handle {
     hipEvent_t scratchDone = nullptr;
     hipStream_t scratchStream = nullptr;
     bool scratchPending = false;
-    // Every cached buffer carries the bytes it holds (0: not allocated).  ensure_buffers grows a
-    // buffer whose held size is below what the current parameters and shape need; dsx_workspace_bytes
-    // is the sum of these fields.
-    uint8_t *dL = nullptr, *dR = nullptr;
-    int16_t *dFixed = nullptr;
-    float *dFloat = nullptr;
-    size_t stagingBytes = 0;     // dL + dR + dFixed + dFloat (dsx_compute_host)
-    uint8_t *dConf = nullptr;    // dsx_compute_conf_host: the confidence map
-    size_t dConfBytes = 0;
-    uint8_t *pfBuf = nullptr;    // prefilter: the filtered left views of every frame, then the right views
-    size_t pfBytes = 0;          //   (rows pf_pitch(W) apart)
-    uint32_t *lrKeys = nullptr;  // LR check: right-view winner keys per pixel (atomicMin target)
-    int16_t *dStar = nullptr;    // LR check: left winners (or -1) for lr_fixup
-    size_t lrKeysBytes = 0, dStarBytes = 0;
-    void *vol = nullptr;
-    size_t vol_bytes = 0;
-    void *btWs = nullptr;  // DSX_COST_BT: prep records of both views | horizontal sums
-    size_t btWsBytes = 0;
-    void *censusWs = nullptr;  // census costs: the code plane of the left view | of the right view
-    size_t censusWsBytes = 0;
-    int16_t *postIn = nullptr;  // sgbm_post: the matcher's int16 maps (postFrames frames)
-    void *postWs = nullptr;     // sgbm_post: median | speckle components
-    size_t postInBytes = 0, postWsBytes = 0;
-    int postFrames = 0;
-    float *ppDisp = nullptr;    // dsx_process_pair_device: the matcher's float map (H x W, fast mode)
-    int16_t *ppFixed = nullptr; // dsx_process_pair_device: the matcher's x16 map (H x W, full mode)
-    size_t ppDispBytes = 0, ppFixedBytes = 0;
+    // The cached buffers, named once (DSX_BUFS).  begin_call drops them all when the shape or the geometry
+    // changes, ensure_buffers grows those the call's plan names, dsx_workspace_bytes sums what they hold.
+    //   stageL / R / Fixed / Float, dConf: dsx_compute_host's views and maps, dsx_compute_conf_host's map
+    //   pfBuf: the filtered left views of every frame, then the right views (rows pf_pitch(W) apart)
+    //   lrKeys: right-view winner keys per pixel (atomicMin target), two halves of lrFrames frames;  dStar: left
+    //   winners (or -1);  vol: one frame's cost volume;  btWs: BT prep records | horizontal sums;  censusWs: codes L | R
+    //   postIn, postWs: sgbm_post's input maps of every frame; median | speckle components
+    //   ppDisp, ppFixed, ppWs: dsx_process_pair_device's float map (fast), x16 map (full), workspace
+    //   sgmS: SGM path sums [H][W][Dp] u32 (sequential);  sgmL: ndir x [H][W][Dp] u16 L_r (concurrent)
+#define DSX_BUFS(X)                                                                                             \
+    X(stageL) X(stageR) X(stageFixed) X(stageFloat) X(dConf) X(pfBuf) X(lrKeys) X(dStar) X(vol) X(btWs) X(censusWs) \
+    X(postIn) X(postWs) X(ppDisp) X(ppFixed) X(ppWs) X(sgmS) X(sgmL)
+#define X(name) DevBuf name;
+    DSX_BUFS(X)
+#undef X
     const uint32_t *lastKeys = nullptr;  // the last fused call's LR key half (run, defer_lr)
     const int16_t *lastDstar = nullptr;
     int lastKshift = 0;
-    void *ppWs = nullptr;       // dsx_process_pair_device: post-processing workspace
-    size_t ppWsBytes = 0;
-    uint32_t *sgmS = nullptr;  // SGM path sums [H][W][Dp] u32 (sequential directions)
-    uint16_t *sgmL = nullptr;  // SGM L_r per direction, ndir x [H][W][Dp] u16 (concurrent directions)
-    size_t sgmSBytes = 0, sgmLBytes = 0;  // sgmL follows the direction count of the aggregation mode
     // timing
     std::vector<std::string> knames;
     std::vector<double> ktotal;
@@ -249,157 +209,82 @@ struct dsx_handle {
 
 namespace {
 
+template <class F>
+void for_each_buf(dsx_handle *h, F f) {
+#define X(name) f(h->name);
+    DSX_BUFS(X)
+#undef X
+}
+
 void free_buffers(dsx_handle *h) {
-    (void)hipFree(h->dL);
-    (void)hipFree(h->dR);
-    (void)hipFree(h->dFixed);
-    (void)hipFree(h->dFloat);
-    (void)hipFree(h->dConf);
-    h->dConf = nullptr;
-    h->dConfBytes = 0;
-    (void)hipFree(h->pfBuf);
-    h->pfBuf = nullptr;
-    h->pfBytes = 0;
-    (void)hipFree(h->lrKeys);
-    (void)hipFree(h->dStar);
-    (void)hipFree(h->vol);
-    (void)hipFree(h->btWs);
-    h->btWs = nullptr;
-    (void)hipFree(h->censusWs);
-    h->censusWs = nullptr;
-    h->censusWsBytes = 0;
-    (void)hipFree(h->postIn);
-    (void)hipFree(h->postWs);
-    h->postIn = nullptr;
-    h->postWs = nullptr;
-    h->postFrames = 0;
-    (void)hipFree(h->sgmS);
-    h->sgmS = nullptr;
-    (void)hipFree(h->ppDisp);
-    (void)hipFree(h->ppFixed);
-    (void)hipFree(h->ppWs);
-    h->ppDisp = nullptr;
-    h->ppFixed = nullptr;
-    h->ppWs = nullptr;
-    h->ppWsBytes = 0;
-    (void)hipFree(h->sgmL);
-    h->sgmL = nullptr;
-    h->dL = h->dR = nullptr;
-    h->dFixed = nullptr;
-    h->dFloat = nullptr;
-    h->lrKeys = nullptr;
-    h->dStar = nullptr;
-    h->vol = nullptr;
-    h->vol_bytes = 0;
-    h->stagingBytes = h->lrKeysBytes = h->dStarBytes = h->btWsBytes = h->postInBytes = h->postWsBytes = 0;
-    h->ppDispBytes = h->ppFixedBytes = h->sgmSBytes = h->sgmLBytes = 0;
+    for_each_buf(h, [](DevBuf &b) { b.release(); });
     h->cH = h->cW = h->cDp = h->cCostBytes = 0;
     h->lrFrames = 0;
     h->lrDirty[0] = h->lrDirty[1] = 0;
     h->scratchPending = false;
 }
 
-int sgm_p1(const dsx_handle *h) { return h->p.p1 > 0 ? h->p.p1 : 8 * h->p.block_size * h->p.block_size; }
-int sgm_p2(const dsx_handle *h) { return h->p.p2 > 0 ? h->p.p2 : 32 * h->p.block_size * h->p.block_size; }
+int cost_bytes(const dsx_params &p) { return p.cost == DSX_COST_SSD ? 4 : 2; }
 
-// All directions in one launch with u16 L_r per direction while max cost + P2 stays below 0xFFFF
-// (L_r <= C + P2; the default P2 = 32 bs^2 always does), else the sequential u32 accumulation.
-// DSX_SGM_SEQ=1 forces the sequential form.
-bool sgm_concurrent(const dsx_handle *h) {
-    static const bool seq = [] {
-        const char *e = getenv("DSX_SGM_SEQ");
-        return e && *e == '1';
-    }();
-    return !seq && max_cost(h->p) + (uint64_t)sgm_p2(h) < 0xFFFFull;
-}
-
-// Grows a cached buffer to at least `need` bytes (it may stay larger; the contents are scratch and
-// are not kept).  hipFree waits for the device, so no earlier launch still uses the old block.
 // Row pitch of the filtered images: whole 16-B groups, so every row takes the wide stores.
 int64_t pf_pitch(int W) { return ((int64_t)W + 15) & ~(int64_t)15; }
 
-template <class T>
-int grow(T *&buf, size_t &held, size_t need) {
-    if (held >= need) return DSX_OK;
-    (void)hipFree(buf);
-    buf = nullptr;
-    held = 0;
-    DSX_HIP(hipMalloc(&buf, need));
-    held = need;
+// New LR buffers of `nframes` frames: every key ~0 (the passes restore that after every frame), both halves clean.
+int init_lr_keys(dsx_handle *h, int nframes) {
+    // The handle's streams are non-blocking, so the fill must have landed before any later launch:
+    // wait for it here (allocation time only)
+    DSX_HIP(hipMemsetAsync(h->lrKeys.ptr, 0xFF, h->lrKeys.held, nullptr));
+    DSX_HIP(hipStreamSynchronize(nullptr));
+    h->lrFrames = nframes;
+    h->lrParity = 0;
+    h->lrDirty[0] = h->lrDirty[1] = 0;
     return DSX_OK;
 }
 
-// conf: the call runs the confidence variant (a confidence output, or the handle's threshold > 0)
-int ensure_buffers(dsx_handle *h, int H, int W, bool host_staging, int nframes = 1, bool conf = false) {
-    const int cbytes = h->p.cost == DSX_COST_SSD ? 4 : 2;
-    if (h->cH != H || h->cW != W || h->cDp != h->g.Dp || h->cCostBytes != cbytes) free_buffers(h);
-    const size_t n = (size_t)H * W;
-
-    if (host_staging && !h->dL) {
-        DSX_HIP(hipMalloc(&h->dL, n));
-        DSX_HIP(hipMalloc(&h->dR, n));
-        DSX_HIP(hipMalloc(&h->dFixed, n * 2));
-        DSX_HIP(hipMalloc(&h->dFloat, n * 4));
-        h->stagingBytes = n * (1 + 1 + 2 + 4);
-    }
-    const bool fused = h->p.path == DSX_PATH_FUSED && !h->p.aggregation && !volume_only(h->p.cost);
-    const bool lr_any = h->p.disp12_max_diff >= 0 || h->p.lr_form == DSX_LR_FORM_SGBM;  // OpenCV's form: always on
-    if (lr_any && fused && h->lrFrames < nframes) {
-        (void)hipFree(h->lrKeys);
-        (void)hipFree(h->dStar);
-        h->lrKeys = nullptr;
-        h->dStar = nullptr;
-        h->lrFrames = 0;
-        h->lrKeysBytes = h->dStarBytes = 0;
-        DSX_HIP(hipMalloc(&h->lrKeys, 2 * n * nframes * 4));  // two halves: this frame / next frame
-        h->lrKeysBytes = 2 * n * nframes * 4;
-        DSX_HIP(hipMalloc(&h->dStar, n * nframes * 2));
-        h->dStarBytes = n * nframes * 2;
-        // lr_fixup restores ~0 after every frame.  The handle's streams are non-blocking, so the
-        // fill must have landed before any later launch: wait for it here (allocation time only)
-        DSX_HIP(hipMemsetAsync(h->lrKeys, 0xFF, 2 * n * nframes * 4, nullptr));
-        DSX_HIP(hipStreamSynchronize(nullptr));
-        h->lrFrames = nframes;
-        h->lrParity = 0;
-        h->lrDirty[0] = h->lrDirty[1] = 0;
-    }
-
-    const bool bt = h->p.cost == DSX_COST_BT;
+// Grows the buffers the plan names to what the call needs at H x W (other translation units' sizes included).
+int ensure_buffers(dsx_handle *h, int H, int W, const dsx::CallPlan &pl) {
+    const size_t n = (size_t)H * W, nf = (size_t)pl.nframes;
+    const auto need = [&pl](uint32_t b) { return (pl.buffers & b) != 0; };
     int rc = DSX_OK;
-    if (h->pf.type != DSX_PREFILTER_NONE &&
-        (rc = grow(h->pfBuf, h->pfBytes, 2 * (size_t)nframes * H * (size_t)pf_pitch(W))))
-        return rc;
-    if ((!fused || conf) && (rc = grow(h->vol, h->vol_bytes, n * h->gv.Dp * cbytes))) return rc;
-    if (bt && (rc = grow(h->btWs, h->btWsBytes, dsx::bt_workspace(H, W, h->g.Dp)))) return rc;
-    if (is_census(h->p.cost) &&
-        (rc = grow(h->censusWs, h->censusWsBytes, 2 * n * dsx::census_code_bytes(h->p.cost))))
-        return rc;
-    if (h->p.sgbm_post && h->postFrames < nframes) {
-        (void)hipFree(h->postIn);
-        h->postIn = nullptr;
-        h->postFrames = 0;
-        h->postInBytes = 0;
-        DSX_HIP(hipMalloc(&h->postIn, n * nframes * 2));
-        h->postInBytes = n * nframes * 2;
-        h->postFrames = nframes;
-    }
-    if (h->p.sgbm_post && (rc = grow(h->postWs, h->postWsBytes, dsx::sgbm_post_workspace(H, W)))) return rc;
-    if (h->p.aggregation) {
-        if (sgm_concurrent(h)) {
-            // one u16 plane set per direction: the buffer follows the mode's direction count
-            // (sgm_paths_all writes L + dir * lstride for every dir below nd)
-            const int *set;
-            const int nd = sgm_set(h->p.aggregation, &set);
-            if ((rc = grow(h->sgmL, h->sgmLBytes, (size_t)nd * n * h->g.Dp * 2))) return rc;
-        } else if ((rc = grow(h->sgmS, h->sgmSBytes, n * h->g.Dp * 4))) {
+    if (need(dsx::BUF_LR)) {
+        bool fresh = false;  // two key halves: this frame / next frame
+        if ((rc = h->lrKeys.grow(2 * n * nf * 4, &fresh)) || (rc = h->dStar.grow(n * nf * 2)) ||
+            (fresh && (rc = init_lr_keys(h, pl.nframes)))) {
+            h->lrKeys.release();  // never keys without their fill and their frame count
+            h->lrFrames = 0;
             return rc;
         }
     }
+    if (need(dsx::BUF_PREFILTER) && (rc = h->pfBuf.grow(2 * nf * H * (size_t)pf_pitch(W)))) return rc;
+    if (need(dsx::BUF_VOLUME) && (rc = h->vol.grow(n * h->gv.Dp * cost_bytes(h->p)))) return rc;
+    if (need(dsx::BUF_BT) && (rc = h->btWs.grow(dsx::bt_workspace(H, W, h->g.Dp)))) return rc;
+    if (need(dsx::BUF_CENSUS) && (rc = h->censusWs.grow(2 * n * dsx::census_code_bytes(h->p.cost)))) return rc;
+    if (need(dsx::BUF_POST) &&
+        ((rc = h->postIn.grow(n * nf * 2)) || (rc = h->postWs.grow(dsx::sgbm_post_workspace(H, W)))))
+        return rc;
+    // one u16 plane set per direction: the buffer follows the mode's direction count
+    // (sgm_paths_all writes L + dir * lstride for every dir below the count)
+    if (need(dsx::BUF_SGM_L) && (rc = h->sgmL.grow((size_t)pl.sgm_ndir * n * h->g.Dp * 2))) return rc;
+    if (need(dsx::BUF_SGM_S) && (rc = h->sgmS.grow(n * h->g.Dp * 4))) return rc;
+    if (need(dsx::BUF_PAIR_DISP) && (rc = h->ppDisp.grow(n * 4))) return rc;
+    if (need(dsx::BUF_PAIR_FIXED) && (rc = h->ppFixed.grow(n * 2))) return rc;
+    if (need(dsx::BUF_PAIR_WS) && (rc = h->ppWs.grow(dsx::post_full_workspace(H, W, std::max(0, h->p.num_disp)))))
+        return rc;
     h->cH = H;
     h->cW = W;
     h->cDp = h->g.Dp;
-    h->cCostBytes = cbytes;
+    h->cCostBytes = cost_bytes(h->p);
     return DSX_OK;
+}
+
+// The front of every handle call, after its argument checks: the handle's device, the call's plan, and the
+// buffer cache at the call's shape.  The cache is invalidated here and nowhere else, before anything is grown.
+int begin_call(dsx_handle *h, int kind, bool conf_out, int nframes, int H, int W, dsx::CallPlan &pl) {
+    DSX_HIP(hipSetDevice(h->device));
+    static const bool sgm_seq = env_flag("DSX_SGM_SEQ");
+    pl = dsx::plan_call(h->p, h->pf, h->cf, kind, conf_out, nframes, sgm_seq);
+    if (h->cH != H || h->cW != W || h->cDp != h->g.Dp || h->cCostBytes != cost_bytes(h->p)) free_buffers(h);
+    return ensure_buffers(h, H, W, pl);
 }
 
 uint32_t pad_value(dsx_handle *h, int DB) {
@@ -588,9 +473,6 @@ int check_fill_shape(int64_t H, int64_t W) {
     return DSX_OK;
 }
 
-// A call runs K2's confidence variant when it is handed a map or the handle's threshold is on.
-bool conf_call(const dsx_handle *h, const void *outConf) { return outConf != nullptr || h->cf.threshold > 0; }
-
 // Orders a call that touches handle scratch on `st` after the previous such call on another stream.
 int wait_scratch(dsx_handle *h, hipStream_t st) {
     if (h->scratchPending && h->scratchStream != st) DSX_HIP(hipStreamWaitEvent(st, h->scratchDone, 0));
@@ -607,8 +489,8 @@ int run_prefilter(dsx_handle *h, const void *&dL, const void *&dR, int H, int W,
     a.src[1] = static_cast<const uint8_t *>(dR);
     a.stride = stride;
     a.frame_stride = nframes > 1 ? frame_stride : 0;
-    a.dst[0] = h->pfBuf;
-    a.dst[1] = h->pfBuf + (size_t)nframes * H * P;
+    a.dst[0] = h->pfBuf.as<uint8_t>();
+    a.dst[1] = a.dst[0] + (size_t)nframes * H * P;
     a.dpitch = P;
     a.dframe = (int64_t)H * P;
     a.dwidth = (int)P;
@@ -634,19 +516,15 @@ int census_seg() {
     return v == 16 || v == 32 || v == 64 ? v : 0;
 }
 
-int run_right_pass(dsx_handle *h, const void *dL, const void *dR, int H, int W, int64_t stride, int16_t *out,
-                   hipStream_t st) {
+int run_right_pass(dsx_handle *h, const dsx::CallPlan &pl, const void *dL, const void *dR, int H, int W,
+                   int64_t stride, int16_t *out, hipStream_t st) {
     if (volume_only(h->p.cost))
         return fail(DSX_EINVAL, "the right-view map is a block-matching (SAD/SSD) pass");
-    const bool pf = h->pf.type != DSX_PREFILTER_NONE;
-    ScratchRecord rec_(h, st, false);
-    if (pf) {
-        int rc = wait_scratch(h, st);
-        if (rc) return rc;
-        rec_.active = true;
-        int64_t fs = 0;
-        if ((rc = run_prefilter(h, dL, dR, H, W, stride, st, 1, fs))) return rc;
-    }
+    int rc = DSX_OK;
+    if (pl.scratch && (rc = wait_scratch(h, st))) return rc;
+    ScratchRecord rec_(h, st, pl.scratch);
+    int64_t fs = 0;
+    if (pl.prefilter && (rc = run_prefilter(h, dL, dR, H, W, stride, st, 1, fs))) return rc;
     dsx::Bm2Args a = base_args(h, H, W, stride);
     a.side = dsx::SIDE_RIGHT;
     a.ref = static_cast<const uint8_t *>(dR);
@@ -657,290 +535,310 @@ int run_right_pass(dsx_handle *h, const void *dL, const void *dR, int H, int W, 
     return rec_.finish();
 }
 
-// nframes frames: inputs frame_stride bytes apart, outputs (and LR buffers) H * W elements apart
-// defer_lr (dsx_process_pair_device): the fused pass's left-right check is left to the caller's next
-// kernel (spk_tile applies it while loading the map): no lr_fixup launch; h->lastKeys / lastDstar
-// name this call's key half and winners.
-int run(dsx_handle *h, const void *dL, const void *dR, int H, int W, int64_t stride, void *outFixed, void *outFloat,
-        hipStream_t st, int nframes = 1, int64_t frame_stride = 0, bool defer_lr = false, void *outConf = nullptr) {
-    const int radius = h->p.block_size / 2;
-    const bool ssd = h->p.cost == DSX_COST_SSD;
-    const bool bt = h->p.cost == DSX_COST_BT;  // BT costs exist only as a volume
-    // sgbm_post: the matcher writes int16 maps into postIn, the tail then writes the outputs
-    void *const finalFixed = outFixed, *const finalFloat = outFloat;
-    const bool census = is_census(h->p.cost);  // so do census costs
-    // the confidence variant lives in K2: such a call runs the volume path on any handle
-    const bool conf = conf_call(h, outConf);
-    const bool fused = h->p.path == DSX_PATH_FUSED && !h->p.aggregation && !volume_only(h->p.cost) && !conf;
-    const dsx::Geometry &gv = h->gv;
-    const bool lr_sg = h->p.lr_form == DSX_LR_FORM_SGBM;  // OpenCV's LR form (always on)
-    const bool pf = h->pf.type != DSX_PREFILTER_NONE;  // the filtered images are handle scratch too
-    const bool scratch = h->p.disp12_max_diff >= 0 || lr_sg || !fused || h->p.sgbm_post || pf;
-    if (scratch) {
-        int rc = wait_scratch(h, st);
-        if (rc) return rc;
+// One matcher call as run()'s stages see it: the inputs after the prefilter and the matcher kernels' outputs
+// (with sgbm_post the handle's int16 maps); frames frame_stride bytes apart, outputs H * W elements apart.
+struct Call {
+    dsx_handle *h;
+    const dsx::CallPlan &pl;
+    const void *dL, *dR;
+    int H, W;
+    int64_t stride, frame_stride;
+    void *outFixed, *outFloat, *outConf;
+    hipStream_t st;
+    bool defer_lr;
+    const uint8_t *view(const void *base, int f) const { return static_cast<const uint8_t *>(base) + f * frame_stride; }
+};
+
+// The fused pass's LR keys are double-buffered: a call fills one half of lrKeys, its fix-up consumes it,
+// and the next call's left pass resets it (every frame a call dirtied, however many the next call has).
+struct LrHalves {
+    uint32_t *keys, *reset;  // this call's half; the other one, with reset_n keys of the previous call not reset yet
+    int64_t reset_n;
+};
+LrHalves lr_halves(const dsx_handle *h, int H, int W) {
+    const size_t half = (size_t)H * W * h->lrFrames;
+    const int P = h->lrParity;
+    uint32_t *k = h->lrKeys.as<uint32_t>();
+    return {k + P * half, k + (P ^ 1) * half, (int64_t)H * W * h->lrDirty[P ^ 1]};
+}
+// after the launches of a call that dirtied nframes frames of its half and reset the other
+void lr_advance(dsx_handle *h, int nframes) {
+    const int P = h->lrParity;
+    h->lrDirty[P ^ 1] = 0;
+    h->lrDirty[P] = nframes;
+    h->lrParity = P ^ 1;
+}
+
+// The fused pass and its LR fix-up.  defer_lr (dsx_process_pair_device): the left-right check is left to
+// the caller's next kernel (spk_tile applies it while loading the map): no fix-up launch; h->lastKeys /
+// lastDstar name this call's key half and winners.
+int run_fused(const Call &c) {
+    dsx_handle *h = c.h;
+    const int H = c.H, W = c.W, nframes = c.pl.nframes, lr = c.pl.lr;
+    const DsxEnv env = dsx_env();
+    dsx::Bm2Args a = base_args(h, H, W, c.stride, env);
+    a.side = dsx::SIDE_LEFT;
+    a.ref = static_cast<const uint8_t *>(c.dL);
+    a.src = static_cast<const uint8_t *>(c.dR);
+    a.out_fixed = static_cast<int16_t *>(c.outFixed);
+    a.out_float = static_cast<float *>(c.outFloat);
+    a.nframes = nframes;
+    a.frame_stride = c.frame_stride;
+    LrHalves k{};
+    int reset_rows = 0;  // rows lr_fixup resets when the left pass does not (DSX_RESET_LEFT 0)
+    if (lr != dsx::LR_NONE) {
+        // bm: the left pass also builds the right-view winners for lr_fixup.  sgbm (OpenCV's form): unique winners
+        // scatter (cost, d) into the keys for lr_fixup_sgbm, the x16 outputs stay in dStar.  Both reset the other half.
+        k = lr_halves(h, H, W);
+        (lr == dsx::LR_BM ? a.lr_keys : a.sg_keys) = k.keys;
+        a.lr_reset = k.reset;
+        a.lr_reset_n = (lr == dsx::LR_SGBM || DSX_RESET_LEFT) ? k.reset_n : 0;
+        reset_rows = DSX_RESET_LEFT ? 0 : H * h->lrDirty[h->lrParity ^ 1];
+        a.dstar = h->dStar.as<int16_t>();
+        a.kshift = h->g.kind != dsx::BM_SAD ? h->g.DB : 16;  // u32 layouts: (C << DB) | d
     }
-    ScratchRecord rec_(h, st, scratch);  // on every exit once launches may have been enqueued
-    if (h->p.sgbm_post) {
-        outFixed = h->postIn;
-        outFloat = nullptr;
-    }
-    const uint8_t *texL = nullptr;  // the filtered left views, for the texture mask
-    if (pf) {
-        int rc = run_prefilter(h, dL, dR, H, W, stride, st, nframes, frame_stride);
-        if (rc) return rc;
-        texL = static_cast<const uint8_t *>(dL);
-    }
-    if (fused) {
-        const bool lr = h->p.disp12_max_diff >= 0 && !lr_sg;
-        const DsxEnv env = dsx_env();
-        dsx::Bm2Args a = base_args(h, H, W, stride, env);
-        a.side = dsx::SIDE_LEFT;
-        a.ref = static_cast<const uint8_t *>(dL);
-        a.src = static_cast<const uint8_t *>(dR);
-        a.out_fixed = static_cast<int16_t *>(outFixed);
-        a.out_float = static_cast<float *>(outFloat);
-        a.nframes = nframes;
-        a.frame_stride = frame_stride;
-        if (lr) {
-            // the left pass also builds the right-view winners (every strip: a right pixel's
-            // diagonal starts left of the valid band); lr_fixup applies the check afterwards
-            a.side = dsx::SIDE_LEFT_LR;
-            a.lr_keys = h->lrKeys + (size_t)h->lrParity * H * W * h->lrFrames;
-            // the other half holds the keys of the previous call (consumed by its lr_fixup, which
-            // precedes this launch): the left pass resets them for the next call
-            a.lr_reset = h->lrKeys + (size_t)(h->lrParity ^ 1) * H * W * h->lrFrames;
-            a.lr_reset_n = DSX_RESET_LEFT ? (int64_t)H * W * h->lrDirty[h->lrParity ^ 1] : 0;
-            a.dstar = h->dStar;
-            a.kshift = h->g.kind != dsx::BM_SAD ? h->g.DB : 16;  // u32 layouts: (C << DB) | d
-        } else {
-            if (lr_sg) {
-                // OpenCV's form: unique winners scatter (cost, d) into this call's key half, which
-                // lr_fixup_sgbm tests afterwards; the pass resets the other half (consumed by the
-                // previous call's fix-up) for the next call, and keeps its x16 outputs in dStar
-                a.sg_keys = h->lrKeys + (size_t)h->lrParity * H * W * h->lrFrames;
-                a.lr_reset = h->lrKeys + (size_t)(h->lrParity ^ 1) * H * W * h->lrFrames;
-                a.lr_reset_n = (int64_t)H * W * h->lrDirty[h->lrParity ^ 1];
-                a.dstar = h->dStar;
-                a.kshift = h->g.kind != dsx::BM_SAD ? h->g.DB : 16;
-            }
-            // only strips meeting the valid band [m + D - 1, W - 1 + m] need a search
-            // (stereo_core.py:168 crops the rest; OpenCV's band lies inside it)
-            const int xlo = std::max(0, h->p.min_disp + h->p.num_disp - 1);
-            const int xhi = std::min(W - 1, W - 1 + h->p.min_disp);
-            if (xlo > xhi) {
-                a.strip_begin = 0;
-                a.strip_count = 0;
-            } else {
-                a.strip_begin = xlo / dsx::kStripWidth;
-                a.strip_count = xhi / dsx::kStripWidth + 1 - a.strip_begin;
-            }
-        }
-        uint64_t *tl = nullptr;
-        const char *tlpath = env.timeline;
-        if (tlpath && *tlpath) DSX_HIP(hipMalloc(&tl, 12 * 8 * 65536));
-        if (tl) DSX_HIP(hipMemsetAsync(tl, 0, 12 * 8 * 65536, st));
-        a.timeline = tl;
-        DSX_LAUNCH(h, "bm_pass_left", st, dsx::launch_bm2(radius, h->g.kind, h->g.NW, a, st));
-        h->lastKeys = lr_sg ? a.sg_keys : (lr ? a.lr_keys : nullptr);
-        h->lastDstar = h->dStar;
-        h->lastKshift = a.kshift;
-        if (lr_sg) {
-            const int P = h->lrParity;
-            if (!defer_lr)
-                DSX_LAUNCH(h, "lr_fixup_sgbm", st,
-                           dsx::launch_lr_fixup_sgbm(h->dStar, a.sg_keys, H * nframes, W, h->p.min_disp,
-                                                     h->p.disp12_max_diff, a.kshift, a.out_fixed, a.out_float, st));
-            h->lrDirty[P ^ 1] = 0;
-            h->lrDirty[P] = nframes;
-            h->lrParity = P ^ 1;
-        }
-        if (lr) {
-            // this call dirties nframes frames of half P; its left pass has reset every dirty frame
-            // of the other half (consumed by the previous call), however many frames that call had
-            const int P = h->lrParity;
-            if (!defer_lr || !DSX_RESET_LEFT)
-                DSX_LAUNCH(h, "lr_fixup", st,
-                           dsx::launch_lr_fixup(h->dStar, a.lr_keys, a.lr_reset,
-                                                DSX_RESET_LEFT ? 0 : H * h->lrDirty[P ^ 1], H * nframes, W,
-                                                h->p.min_disp, h->p.disp12_max_diff, a.kshift, a.out_fixed,
-                                                a.out_float, st));
-            h->lrDirty[P ^ 1] = 0;
-            h->lrDirty[P] = nframes;
-            h->lrParity = P ^ 1;
-        }
-        if (tl) {
-            std::vector<uint64_t> host(12 * 65536);
-            DSX_HIP(hipStreamSynchronize(st));
-            DSX_HIP(hipMemcpy(host.data(), tl, host.size() * 8, hipMemcpyDeviceToHost));
-            FILE *f = fopen(tlpath, "wb");
-            if (f) {
-                fwrite(host.data(), 8, host.size(), f);
-                fclose(f);
-            }
-            (void)hipFree(tl);
-        }
+    if (lr == dsx::LR_BM) {
+        // every strip: a right pixel's diagonal starts left of the valid band
+        a.side = dsx::SIDE_LEFT_LR;
     } else {
-        // volume path: one K1 + K2 pair per frame (the volume buffer holds one frame)
-        for (int f = 0; f < nframes; ++f) {
-            const size_t fo = (size_t)f * H * W;
-            if (bt) {
-                const size_t n = (size_t)H * W;
-                uint2 *prepL = static_cast<uint2 *>(h->btWs), *prepR = prepL + n;
-                const int ftz = bt_ftzero(h->p);
-                const uint8_t *l = static_cast<const uint8_t *>(dL) + f * frame_stride;
-                const uint8_t *r = static_cast<const uint8_t *>(dR) + f * frame_stride;
-                DSX_LAUNCH(h, "bt_prep", st, dsx::launch_bt_prep(l, stride, H, W, ftz, prepL, st));
-                DSX_LAUNCH(h, "bt_prep", st, dsx::launch_bt_prep(r, stride, H, W, ftz, prepR, st));
-                dsx::BtArgs b{};
-                b.prepL = prepL;
-                b.prepR = prepR;
-                b.hs = reinterpret_cast<uint16_t *>(prepR + n);
-                b.vol = h->vol;
-                b.H = H;
-                b.W = W;
-                b.m = h->p.min_disp;
-                b.D = h->p.num_disp;
-                b.Dp = gv.Dp;
-                b.R = radius;
-                b.padv = pad_value(h, gv.DB);
-                DSX_LAUNCH(h, "bt_hsum", st, dsx::launch_bt_volume(b, 0, st));
-                DSX_LAUNCH(h, "bt_vsum", st, dsx::launch_bt_volume(b, 1, st));
-            } else if (census) {
-                const size_t cb = (size_t)H * W * dsx::census_code_bytes(h->p.cost);
-                dsx::CensusArgs c{};
-                c.src[0] = static_cast<const uint8_t *>(dL) + f * frame_stride;
-                c.src[1] = static_cast<const uint8_t *>(dR) + f * frame_stride;
-                c.stride = stride;
-                c.dst[0] = h->censusWs;
-                c.dst[1] = static_cast<uint8_t *>(h->censusWs) + cb;
-                c.nviews = 2;
-                c.H = H;
-                c.W = W;
-                c.window = h->p.cost;
-                c.out64 = h->p.cost == DSX_COST_CENSUS9X7;
-                DSX_LAUNCH(h, "census_transform", st, dsx::launch_census_transform(c, st));
-                dsx::CensusVolArgs v{};
-                v.codeL = c.dst[0];
-                v.codeR = c.dst[1];
-                v.vol = h->vol;
-                v.H = H;
-                v.W = W;
-                v.m = h->p.min_disp;
-                v.D = h->p.num_disp;
-                v.Dp = gv.Dp;
-                v.R = radius;
-                v.window = h->p.cost;
-                v.seg = census_seg();
-                v.padv = pad_value(h, gv.DB);
-                DSX_LAUNCH(h, "census_volume", st, dsx::launch_census_volume(v, st));
-            } else {
-                dsx::Bm2Args a = base_args(h, H, W, stride);
-                a.side = dsx::SIDE_VOLUME;
-                a.ref = static_cast<const uint8_t *>(dL) + f * frame_stride;
-                a.src = static_cast<const uint8_t *>(dR) + f * frame_stride;
-                a.vol = h->vol;
-                a.padv = pad_value(h, gv.DB);
-                DSX_LAUNCH(h, "cost_volume", st, dsx::launch_bm2(radius, ssd ? dsx::BM_SSD : dsx::BM_SAD, gv.NW, a, st));
-            }
-            const bool agg = h->p.aggregation != DSX_AGG_NONE;
-            const bool agg_all = agg && sgm_concurrent(h);
-            const int *set = nullptr;
-            const int nd = agg ? sgm_set(h->p.aggregation, &set) : 0;
-            if (agg_all) {
-                // every path of every direction in one launch, L_r per direction (u16)
-                dsx::SgmAllArgs sa{};
-                sa.C = static_cast<const uint16_t *>(h->vol);
-                sa.L = h->sgmL;
-                sa.lstride = (size_t)H * W * h->g.Dp;
-                sa.H = H;
-                sa.W = W;
-                sa.D = h->p.num_disp;
-                sa.Dp = h->g.Dp;
-                sa.ndir = nd;
-                sa.poff[0] = 0;
-                for (int i = 0; i < nd; ++i) {
-                    sa.dx[i] = kSgmDirs[set[i]][0];
-                    sa.dy[i] = kSgmDirs[set[i]][1];
-                    sa.poff[i + 1] = sa.poff[i] + dsx::sgm_num_paths_host(H, W, sa.dx[i], sa.dy[i]);
-                }
-                sa.P1 = sgm_p1(h);
-                sa.P2 = sgm_p2(h);
-                DSX_LAUNCH(h, "sgm_paths", st, dsx::launch_sgm_all(sa, st));
-            } else if (agg) {
-                // SGM: one pass per direction of the mode's path set (oracle/sgm.py DIRECTIONS)
-                dsx::SgmArgs sa{};
-                sa.C = static_cast<const uint16_t *>(h->vol);
-                sa.S = h->sgmS;
-                sa.H = H;
-                sa.W = W;
-                sa.D = h->p.num_disp;
-                sa.Dp = h->g.Dp;
-                sa.P1 = sgm_p1(h);
-                sa.P2 = sgm_p2(h);
-                sa.pads = (uint32_t)((1ull << (32 - h->g.DB)) - 1ull);
-                for (int i = 0; i < nd; ++i) {
-                    sa.dx = kSgmDirs[set[i]][0];
-                    sa.dy = kSgmDirs[set[i]][1];
-                    DSX_LAUNCH(h, "sgm_path", st, dsx::launch_sgm_path(sa, i == 0, st));
-                }
-            }
-            dsx::VolArgs v{};
-            v.vol = agg_all ? static_cast<const void *>(h->sgmL) : (agg ? static_cast<const void *>(h->sgmS) : h->vol);
-            v.nsum = agg_all ? nd : 0;
-            v.sstride = (size_t)H * W * gv.Dp;
-            v.H = H;
-            v.W = W;
-            v.m = h->p.min_disp;
-            v.D = h->p.num_disp;
-            v.Dp = gv.Dp;
-            v.DB = gv.DB;
-            v.TPP = gv.TPP;
-            v.uniq = h->p.uniqueness_ratio;
-            v.lr = h->p.disp12_max_diff;
-            v.lr_form = h->p.lr_form;
-            v.subpix = h->p.subpixel;
-            v.float_mode = h->p.float_mode;
-            v.out_fixed = outFixed ? static_cast<int16_t *>(outFixed) + fo : nullptr;
-            v.out_float = outFloat ? static_cast<float *>(outFloat) + fo : nullptr;
-            v.conf = conf ? 1 : 0;
-            v.conf_t = h->cf.threshold;
-            v.out_conf = outConf ? static_cast<uint8_t *>(outConf) + fo : nullptr;
-            const bool wide = ssd || agg;  // u32 costs: SSD block costs or SGM path sums
-            if (dsx::volume_smem_bytes(gv.TX, wide, gv.Dp, gv.TPP, W, conf) > 160 * 1024)
-                return fail(DSX_EINVAL, "image too wide for the volume path's row kernel");
-            DSX_LAUNCH(h, "volume_wta", st, dsx::launch_volume_wta(gv.TX, wide, v, st));
+        // only strips meeting the valid band [m + D - 1, W - 1 + m] need a search
+        // (stereo_core.py:168 crops the rest; OpenCV's band lies inside it)
+        const int xlo = std::max(0, h->p.min_disp + h->p.num_disp - 1);
+        const int xhi = std::min(W - 1, W - 1 + h->p.min_disp);
+        a.strip_count = 0;
+        if (xlo <= xhi) {
+            a.strip_begin = xlo / dsx::kStripWidth;
+            a.strip_count = xhi / dsx::kStripWidth + 1 - a.strip_begin;
         }
     }
-    if (pf && h->pf.texture_threshold > 0 && (outFixed || outFloat)) {  // a map-only confidence call has neither
-        // after the last matcher kernel (uniqueness, sub-pixel, LR check), before the sgbm_post tail
-        dsx::TextureArgs t{};
-        t.pref = texL;
-        t.stride = stride;
-        t.frame_stride = frame_stride;
-        t.nframes = nframes;
+    uint64_t *tl = nullptr;
+    const char *tlpath = env.timeline;
+    if (tlpath && *tlpath) DSX_HIP(hipMalloc(&tl, 12 * 8 * 65536));
+    if (tl) DSX_HIP(hipMemsetAsync(tl, 0, 12 * 8 * 65536, c.st));
+    a.timeline = tl;
+    DSX_LAUNCH(h, "bm_pass_left", c.st, dsx::launch_bm2(h->p.block_size / 2, h->g.kind, h->g.NW, a, c.st));
+    h->lastKeys = k.keys;
+    h->lastDstar = h->dStar.as<int16_t>();
+    h->lastKshift = a.kshift;
+    if (lr == dsx::LR_SGBM && !c.defer_lr)
+        DSX_LAUNCH(h, "lr_fixup_sgbm", c.st,
+                   dsx::launch_lr_fixup_sgbm(a.dstar, k.keys, H * nframes, W, h->p.min_disp, h->p.disp12_max_diff,
+                                             a.kshift, a.out_fixed, a.out_float, c.st));
+    if (lr == dsx::LR_BM && (!c.defer_lr || !DSX_RESET_LEFT))
+        DSX_LAUNCH(h, "lr_fixup", c.st,
+                   dsx::launch_lr_fixup(a.dstar, k.keys, k.reset, reset_rows, H * nframes, W, h->p.min_disp,
+                                        h->p.disp12_max_diff, a.kshift, a.out_fixed, a.out_float, c.st));
+    if (lr != dsx::LR_NONE) lr_advance(h, nframes);
+    if (tl) {
+        std::vector<uint64_t> host(12 * 65536);
+        DSX_HIP(hipStreamSynchronize(c.st));
+        DSX_HIP(hipMemcpy(host.data(), tl, host.size() * 8, hipMemcpyDeviceToHost));
+        FILE *f = fopen(tlpath, "wb");
+        if (f) {
+            fwrite(host.data(), 8, host.size(), f);
+            fclose(f);
+        }
+        (void)hipFree(tl);
+    }
+    return DSX_OK;
+}
+
+// the volume, shape and search range of BtArgs / CensusVolArgs
+template <class A>
+void volume_args(const Call &c, A &a) {
+    a.vol = c.h->vol.ptr;
+    a.H = c.H;
+    a.W = c.W;
+    a.m = c.h->p.min_disp;
+    a.D = c.h->p.num_disp;
+    a.Dp = c.h->gv.Dp;
+    a.R = c.h->p.block_size / 2;
+    a.padv = pad_value(c.h, c.h->gv.DB);
+}
+
+// K1 of the volume path: frame f's costs of the plan's builder into the handle's volume
+int build_volume(const Call &c, int f) {
+    dsx_handle *h = c.h;
+    const int H = c.H, W = c.W;
+    const uint8_t *l = c.view(c.dL, f), *r = c.view(c.dR, f);
+    if (c.pl.builder == dsx::BUILD_BT) {
+        const size_t n = (size_t)H * W;
+        uint2 *prepL = h->btWs.as<uint2>(), *prepR = prepL + n;
+        const int ftz = bt_ftzero(h->p);
+        DSX_LAUNCH(h, "bt_prep", c.st, dsx::launch_bt_prep(l, c.stride, H, W, ftz, prepL, c.st));
+        DSX_LAUNCH(h, "bt_prep", c.st, dsx::launch_bt_prep(r, c.stride, H, W, ftz, prepR, c.st));
+        dsx::BtArgs b{};
+        b.prepL = prepL;
+        b.prepR = prepR;
+        b.hs = reinterpret_cast<uint16_t *>(prepR + n);
+        volume_args(c, b);
+        DSX_LAUNCH(h, "bt_hsum", c.st, dsx::launch_bt_volume(b, 0, c.st));
+        DSX_LAUNCH(h, "bt_vsum", c.st, dsx::launch_bt_volume(b, 1, c.st));
+    } else if (c.pl.builder == dsx::BUILD_CENSUS) {
+        dsx::CensusArgs t{};
+        t.src[0] = l;
+        t.src[1] = r;
+        t.stride = c.stride;
+        t.dst[0] = h->censusWs.ptr;
+        t.dst[1] = h->censusWs.as<uint8_t>() + (size_t)H * W * dsx::census_code_bytes(h->p.cost);
+        t.nviews = 2;
         t.H = H;
         t.W = W;
+        t.window = h->p.cost;
+        t.out64 = h->p.cost == DSX_COST_CENSUS9X7;
+        DSX_LAUNCH(h, "census_transform", c.st, dsx::launch_census_transform(t, c.st));
+        dsx::CensusVolArgs v{};
+        v.codeL = t.dst[0];
+        v.codeR = t.dst[1];
+        volume_args(c, v);
+        v.window = h->p.cost;
+        v.seg = census_seg();
+        DSX_LAUNCH(h, "census_volume", c.st, dsx::launch_census_volume(v, c.st));
+    } else {  // SAD / SSD block costs: bm2's volume side
+        dsx::Bm2Args a = base_args(h, H, W, c.stride);
+        a.side = dsx::SIDE_VOLUME;
+        a.ref = l;
+        a.src = r;
+        a.vol = h->vol.ptr;
+        a.padv = pad_value(h, h->gv.DB);
+        const int kind = h->p.cost == DSX_COST_SSD ? dsx::BM_SSD : dsx::BM_SAD;
+        DSX_LAUNCH(h, "cost_volume", c.st, dsx::launch_bm2(h->p.block_size / 2, kind, h->gv.NW, a, c.st));
+    }
+    return DSX_OK;
+}
+
+// SGM over the handle's volume: every path of every direction in one launch with L_r per direction (u16),
+// or one pass per direction of the mode's path set (oracle/sgm.py DIRECTIONS) into u32 sums
+template <class A>
+void sgm_args(const Call &c, A &sa) {
+    sa.C = c.h->vol.as<const uint16_t>();
+    sa.H = c.H;
+    sa.W = c.W;
+    sa.D = c.h->p.num_disp;
+    sa.Dp = c.h->g.Dp;
+    sa.P1 = dsx::sgm_p1(c.h->p);
+    sa.P2 = dsx::sgm_p2(c.h->p);
+}
+int run_sgm(const Call &c) {
+    dsx_handle *h = c.h;
+    const int nd = c.pl.sgm_ndir, *set = c.pl.sgm_dirs;
+    if (c.pl.sgm == dsx::SGM_CONCURRENT) {
+        dsx::SgmAllArgs sa{};
+        sgm_args(c, sa);
+        sa.L = h->sgmL.as<uint16_t>();
+        sa.lstride = (size_t)c.H * c.W * h->g.Dp;
+        sa.ndir = nd;
+        for (int i = 0; i < nd; ++i) {
+            sa.dx[i] = dsx::kSgmDirs[set[i]][0];
+            sa.dy[i] = dsx::kSgmDirs[set[i]][1];
+            sa.poff[i + 1] = sa.poff[i] + dsx::sgm_num_paths_host(c.H, c.W, sa.dx[i], sa.dy[i]);
+        }
+        DSX_LAUNCH(h, "sgm_paths", c.st, dsx::launch_sgm_all(sa, c.st));
+    } else if (c.pl.sgm == dsx::SGM_SEQUENTIAL) {
+        dsx::SgmArgs sa{};
+        sgm_args(c, sa);
+        sa.S = h->sgmS.as<uint32_t>();
+        sa.pads = (uint32_t)((1ull << (32 - h->g.DB)) - 1ull);
+        for (int i = 0; i < nd; ++i) {
+            sa.dx = dsx::kSgmDirs[set[i]][0];
+            sa.dy = dsx::kSgmDirs[set[i]][1];
+            DSX_LAUNCH(h, "sgm_path", c.st, dsx::launch_sgm_path(sa, i == 0, c.st));
+        }
+    }
+    return DSX_OK;
+}
+
+// K2: winner, uniqueness, sub-pixel, LR check and confidence of frame f from the volume or the SGM sums
+int run_volume_wta(const Call &c, int f) {
+    dsx_handle *h = c.h;
+    const dsx::Geometry &gv = h->gv;
+    const size_t fo = (size_t)f * c.H * c.W;
+    const int sgm = c.pl.sgm;
+    dsx::VolArgs v{};
+    v.vol = sgm == dsx::SGM_CONCURRENT ? h->sgmL.ptr : (sgm == dsx::SGM_SEQUENTIAL ? h->sgmS.ptr : h->vol.ptr);
+    v.nsum = sgm == dsx::SGM_CONCURRENT ? c.pl.sgm_ndir : 0;
+    v.sstride = (size_t)c.H * c.W * gv.Dp;
+    v.H = c.H;
+    v.W = c.W;
+    v.m = h->p.min_disp;
+    v.D = h->p.num_disp;
+    v.Dp = gv.Dp;
+    v.DB = gv.DB;
+    v.TPP = gv.TPP;
+    v.uniq = h->p.uniqueness_ratio;
+    v.lr = h->p.disp12_max_diff;
+    v.lr_form = h->p.lr_form;
+    v.subpix = h->p.subpixel;
+    v.float_mode = h->p.float_mode;
+    v.out_fixed = c.outFixed ? static_cast<int16_t *>(c.outFixed) + fo : nullptr;
+    v.out_float = c.outFloat ? static_cast<float *>(c.outFloat) + fo : nullptr;
+    v.conf = c.pl.conf ? 1 : 0;
+    v.conf_t = h->cf.threshold;
+    v.out_conf = c.outConf ? static_cast<uint8_t *>(c.outConf) + fo : nullptr;
+    const bool wide = h->p.cost == DSX_COST_SSD || sgm != dsx::SGM_NONE;  // u32 costs: SSD block costs or SGM path sums
+    if (dsx::volume_smem_bytes(gv.TX, wide, gv.Dp, gv.TPP, c.W, c.pl.conf) > 160 * 1024)
+        return fail(DSX_EINVAL, "image too wide for the volume path's row kernel");
+    DSX_LAUNCH(h, "volume_wta", c.st, dsx::launch_volume_wta(gv.TX, wide, v, c.st));
+    return DSX_OK;
+}
+
+// After the last matcher kernel: the texture mask on its maps, then sgbm_post from the handle's int16 maps.
+int run_tail(const Call &c, void *finalFixed, void *finalFloat) {
+    dsx_handle *h = c.h;
+    if (c.pl.texture && (c.outFixed || c.outFloat)) {  // a map-only confidence call has neither
+        dsx::TextureArgs t{};
+        t.pref = static_cast<const uint8_t *>(c.dL);  // the filtered left views
+        t.stride = c.stride;
+        t.frame_stride = c.frame_stride;
+        t.nframes = c.pl.nframes;
+        t.H = c.H;
+        t.W = c.W;
         t.block = h->p.block_size;
         t.cap = h->pf.cap;
         t.thr = h->pf.texture_threshold;
-        t.out_fixed = static_cast<int16_t *>(outFixed);
-        t.out_float = static_cast<float *>(outFloat);
+        t.out_fixed = static_cast<int16_t *>(c.outFixed);
+        t.out_float = static_cast<float *>(c.outFloat);
         t.inv16 = (h->p.min_disp - 1) * 16;
         t.invf = (float)(h->p.min_disp - 1);
-        DSX_LAUNCH(h, "texture_mask", st, dsx::launch_texture(t, st));
+        DSX_LAUNCH(h, "texture_mask", c.st, dsx::launch_texture(t, c.st));
     }
-    if (h->p.sgbm_post) {
-        for (int f = 0; f < nframes; ++f) {
-            const size_t fo = (size_t)f * H * W;
-            DSX_LAUNCH(h, "sgbm_post", st,
-                       dsx::launch_sgbm_post(h->postIn + fo, H, W, (h->p.min_disp - 1) * 16, h->p.speckle_window_size,
-                                             16 * h->p.speckle_range,
+    if (c.pl.post) {
+        for (int f = 0; f < c.pl.nframes; ++f) {
+            const size_t fo = (size_t)f * c.H * c.W;
+            DSX_LAUNCH(h, "sgbm_post", c.st,
+                       dsx::launch_sgbm_post(h->postIn.as<int16_t>() + fo, c.H, c.W, (h->p.min_disp - 1) * 16,
+                                             h->p.speckle_window_size, 16 * h->p.speckle_range,
                                              finalFixed ? static_cast<int16_t *>(finalFixed) + fo : nullptr,
-                                             finalFloat ? static_cast<float *>(finalFloat) + fo : nullptr, h->postWs,
-                                             st));
+                                             finalFloat ? static_cast<float *>(finalFloat) + fo : nullptr,
+                                             h->postWs.ptr, c.st));
         }
     }
+    return DSX_OK;
+}
+
+// The matcher of a compute, batch or process_pair call, launched stage by stage from the call's plan.
+int run(dsx_handle *h, const dsx::CallPlan &pl, const void *dL, const void *dR, int H, int W, int64_t stride,
+        void *outFixed, void *outFloat, hipStream_t st, int64_t frame_stride = 0, bool defer_lr = false,
+        void *outConf = nullptr) {
+    int rc = DSX_OK;
+    if (pl.scratch && (rc = wait_scratch(h, st))) return rc;
+    ScratchRecord rec_(h, st, pl.scratch);  // on every exit once launches may have been enqueued
+    if (pl.prefilter && (rc = run_prefilter(h, dL, dR, H, W, stride, st, pl.nframes, frame_stride))) return rc;
+    // sgbm_post: the matcher writes int16 maps into postIn, the tail then writes the outputs
+    const Call c{h, pl, dL, dR, H, W, stride, frame_stride, pl.post ? h->postIn.ptr : outFixed,
+                 pl.post ? nullptr : outFloat, outConf, st, defer_lr};
+    if (pl.fused) {
+        if ((rc = run_fused(c))) return rc;
+    } else {
+        // volume path: one K1 (+ SGM) + K2 group per frame (the volume buffer holds one frame)
+        for (int f = 0; f < pl.nframes; ++f) {
+            rc = build_volume(c, f);
+            if (!rc) rc = run_sgm(c);
+            if (!rc) rc = run_volume_wta(c, f);
+            if (rc) return rc;
+        }
+    }
+    if ((rc = run_tail(c, outFixed, outFloat))) return rc;
     return rec_.finish();
 }
 
@@ -951,26 +849,88 @@ int check_shape(int H, int W, int64_t stride) {
     return DSX_OK;
 }
 
-// dsx_compute_host / dsx_compute_conf_host after their argument checks (out_fixed may be NULL only with out_conf)
+// dsx_compute_device, dsx_compute_conf_device (CALL_COMPUTE, one frame) and dsx_compute_batch_device (CALL_BATCH)
+int compute_device(dsx_handle *h, int kind, int nframes, const void *dL, const void *dR, int64_t frame_stride, int H,
+                   int W, int64_t stride, void *out_fixed, void *out_float, void *out_conf, void *hip_stream) {
+    g_err.clear();
+    if (!h) return fail(DSX_EINVAL, "handle is NULL");
+    if (!dL || !dR) return fail(DSX_EINVAL, "input pointers are NULL");
+    if (!out_fixed && !out_float && !out_conf) return fail(DSX_EINVAL, "at least one output is required");
+    if (nframes < 1) return fail(DSX_EINVAL, "nframes must be >= 1");
+    int rc = check_shape(H, W, stride);
+    if (rc) return rc;
+    if (nframes > 1 && frame_stride < (int64_t)(H - 1) * stride + W)
+        return fail(DSX_EINVAL, "frame_stride_bytes smaller than one frame");
+    if (kind == dsx::CALL_BATCH && (int64_t)nframes * H * W > ((int64_t)1 << 31) - 1)
+        return fail(DSX_EINVAL, "nframes * H * W must stay below 2^31 pixels per launch");
+    dsx::CallPlan pl;
+    if ((rc = begin_call(h, kind, out_conf != nullptr, nframes, H, W, pl))) return rc;
+    return run(h, pl, dL, dR, H, W, stride, out_fixed, out_float, static_cast<hipStream_t>(hip_stream), frame_stride,
+               false, out_conf);
+}
+
+// dsx_compute_host / dsx_compute_conf_host (out_fixed may be NULL only with out_conf)
 int compute_host(dsx_handle *h, const uint8_t *L, const uint8_t *R, int H, int W, int64_t stride_bytes,
                  int16_t *out_fixed, float *out_float, uint8_t *out_conf) {
+    g_err.clear();
+    if (!h) return fail(DSX_EINVAL, "handle is NULL");
+    if (!L || !R || (!out_fixed && !out_conf))
+        return fail(DSX_EINVAL, out_conf ? "input pointers are NULL" : "NULL argument (out_fixed is required)");
     int rc = check_shape(H, W, stride_bytes);
     if (rc) return rc;
-    DSX_HIP(hipSetDevice(h->device));
-    rc = ensure_buffers(h, H, W, true, 1, conf_call(h, out_conf));
-    if (rc) return rc;
-    if (out_conf && (rc = grow(h->dConf, h->dConfBytes, (size_t)H * W))) return rc;
+    dsx::CallPlan pl;
+    if ((rc = begin_call(h, dsx::CALL_COMPUTE, out_conf != nullptr, 1, H, W, pl))) return rc;
+    const size_t n = (size_t)H * W;
+    if ((rc = h->stageL.grow(n)) || (rc = h->stageR.grow(n)) || (rc = h->stageFixed.grow(n * 2)) ||
+        (rc = h->stageFloat.grow(n * 4)) || (out_conf && (rc = h->dConf.grow(n))))
+        return rc;
     hipStream_t st = h->stream;
-    DSX_HIP(hipMemcpy2DAsync(h->dL, W, L, stride_bytes, W, H, hipMemcpyHostToDevice, st));
-    DSX_HIP(hipMemcpy2DAsync(h->dR, W, R, stride_bytes, W, H, hipMemcpyHostToDevice, st));
-    rc = run(h, h->dL, h->dR, H, W, W, h->dFixed, out_float ? h->dFloat : nullptr, st, 1, 0, false,
-             out_conf ? h->dConf : nullptr);
+    DSX_HIP(hipMemcpy2DAsync(h->stageL.ptr, W, L, stride_bytes, W, H, hipMemcpyHostToDevice, st));
+    DSX_HIP(hipMemcpy2DAsync(h->stageR.ptr, W, R, stride_bytes, W, H, hipMemcpyHostToDevice, st));
+    rc = run(h, pl, h->stageL.ptr, h->stageR.ptr, H, W, W, h->stageFixed.ptr, out_float ? h->stageFloat.ptr : nullptr,
+             st, 0, false, out_conf ? h->dConf.ptr : nullptr);
     if (rc) return rc;
-    if (out_fixed) DSX_HIP(hipMemcpyAsync(out_fixed, h->dFixed, (size_t)H * W * 2, hipMemcpyDeviceToHost, st));
-    if (out_float) DSX_HIP(hipMemcpyAsync(out_float, h->dFloat, (size_t)H * W * 4, hipMemcpyDeviceToHost, st));
-    if (out_conf) DSX_HIP(hipMemcpyAsync(out_conf, h->dConf, (size_t)H * W, hipMemcpyDeviceToHost, st));
+    if (out_fixed) DSX_HIP(hipMemcpyAsync(out_fixed, h->stageFixed.ptr, n * 2, hipMemcpyDeviceToHost, st));
+    if (out_float) DSX_HIP(hipMemcpyAsync(out_float, h->stageFloat.ptr, n * 4, hipMemcpyDeviceToHost, st));
+    if (out_conf) DSX_HIP(hipMemcpyAsync(out_conf, h->dConf.ptr, n, hipMemcpyDeviceToHost, st));
     DSX_HIP(hipStreamSynchronize(st));
     return DSX_OK;
+}
+
+// the C-ABI's step count (0 adaptive, > 0 that many, < 0 none) as InpaintOpts.steps
+int fill_steps(int32_t steps) { return steps == 0 ? -1 : std::max(0, (int)steps); }
+
+// The shape, the outputs and the depth conversion (PostArgs and PostFullArgs name them alike); depth only
+// when has_depth.
+template <class A>
+void post_args(A &a, const dsx_post_params &pp, int64_t in_pitch, int H, int W, int crop, void *d_out_disp,
+               void *d_out_depth) {
+    a.in_pitch = in_pitch;
+    a.H = H;
+    a.W = W;
+    a.crop = crop;
+    a.out_disp = static_cast<float *>(d_out_disp);
+    a.out_depth = pp.has_depth ? static_cast<float *>(d_out_depth) : nullptr;
+    a.fB = (float)(pp.focal_length * pp.baseline);
+    a.doffs = (float)pp.doffs;
+    a.eps = (float)pp.eps;
+    a.max_depth = (float)pp.max_depth;
+    a.has_max = pp.has_max_depth ? 1 : 0;
+}
+
+// the full chain's filters and hole filling on top; the input and the status key are the caller's
+void post_full_args(dsx::PostFullArgs &a, const dsx_post_params &pp, int64_t in_pitch, int H, int W, int crop,
+                    void *d_out_disp, void *d_out_depth) {
+    post_args(a, pp, in_pitch, H, W, crop, d_out_disp, d_out_depth);
+    a.max_speckle = pp.max_speckle_size;
+    a.max_diff16 = (int)(pp.max_diff * 16);  // int(max_diff * 16), postprocess.py:30
+    a.apply_outliers = pp.apply_outlier_removal ? 1 : 0;
+    a.kernel = pp.outlier_kernel;
+    a.thr = (float)pp.outlier_threshold;
+    a.fill_radius = pp.fill_radius;
+    a.fill_method = pp.fill_method;
+    a.fill_opts.spin_limit = pp.fill_spin_limit;
+    a.fill_opts.steps = fill_steps(pp.fill_steps);
 }
 
 }  // namespace
@@ -1043,7 +1003,7 @@ int dsx_create(int device, const dsx_params *p, dsx_handle **out) {
     h->p = *p;
     dsx_default_confidence(&h->cf);
     pick_geometry(*p, h->g);
-    pick_volume_geometry(*p, h->gv);
+    dsx::pick_volume_geometry(*p, h->gv);
     hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         delete h;
@@ -1068,7 +1028,7 @@ int dsx_set_params(dsx_handle *h, const dsx_params *p) {
     DSX_HIP(hipStreamSynchronize(h->stream));
     h->p = *p;
     pick_geometry(*p, h->g);
-    pick_volume_geometry(*p, h->gv);
+    dsx::pick_volume_geometry(*p, h->gv);
     return DSX_OK;
 }
 
@@ -1131,11 +1091,10 @@ int dsx_texture_sum_device(const void *d_pref, int32_t H, int32_t W, int64_t str
                            int32_t cap, void *d_out_u16, void *hip_stream) {
     g_err.clear();
     if (!d_pref || !d_out_u16) return fail(DSX_EINVAL, "NULL image or output");
-    if (block_size < 1 || block_size > 15 || (block_size & 1) == 0)
-        return fail(DSX_EINVAL, "block_size must be odd and in [1, 15]");
-    if (cap < 1 || cap > 63) return fail(DSX_EINVAL, "cap must be in [1, 63]");
-    int rc = check_shape(H, W, stride_bytes);
+    int rc = check_block_size(block_size);
     if (rc) return rc;
+    if (cap < 1 || cap > 63) return fail(DSX_EINVAL, "cap must be in [1, 63]");
+    if ((rc = check_shape(H, W, stride_bytes))) return rc;
     dsx::TextureArgs t{};
     t.pref = static_cast<const uint8_t *>(d_pref);
     t.stride = stride_bytes;
@@ -1171,16 +1130,8 @@ int dsx_census_device(const void *d_img, int32_t H, int32_t W, int64_t stride_by
 
 int dsx_compute_device(dsx_handle *h, const void *dL, const void *dR, int32_t H, int32_t W, int64_t stride_bytes,
                        void *d_out_fixed, void *d_out_float, void *hip_stream) {
-    g_err.clear();
-    if (!h) return fail(DSX_EINVAL, "handle is NULL");
-    if (!dL || !dR) return fail(DSX_EINVAL, "input pointers are NULL");
-    if (!d_out_fixed && !d_out_float) return fail(DSX_EINVAL, "at least one output is required");
-    int rc = check_shape(H, W, stride_bytes);
-    if (rc) return rc;
-    DSX_HIP(hipSetDevice(h->device));
-    rc = ensure_buffers(h, H, W, false, 1, conf_call(h, nullptr));
-    if (rc) return rc;
-    return run(h, dL, dR, H, W, stride_bytes, d_out_fixed, d_out_float, static_cast<hipStream_t>(hip_stream));
+    return compute_device(h, dsx::CALL_COMPUTE, 1, dL, dR, 0, H, W, stride_bytes, d_out_fixed, d_out_float, nullptr,
+                          hip_stream);
 }
 
 void dsx_default_confidence(dsx_confidence *c) {
@@ -1211,17 +1162,8 @@ int dsx_set_confidence(dsx_handle *h, const dsx_confidence *c) {
 
 int dsx_compute_conf_device(dsx_handle *h, const void *dL, const void *dR, int32_t H, int32_t W, int64_t stride_bytes,
                             void *d_out_fixed, void *d_out_float, void *d_out_conf, void *hip_stream) {
-    if (!d_out_conf) return dsx_compute_device(h, dL, dR, H, W, stride_bytes, d_out_fixed, d_out_float, hip_stream);
-    g_err.clear();
-    if (!h) return fail(DSX_EINVAL, "handle is NULL");
-    if (!dL || !dR) return fail(DSX_EINVAL, "input pointers are NULL");
-    int rc = check_shape(H, W, stride_bytes);
-    if (rc) return rc;
-    DSX_HIP(hipSetDevice(h->device));
-    rc = ensure_buffers(h, H, W, false, 1, true);
-    if (rc) return rc;
-    return run(h, dL, dR, H, W, stride_bytes, d_out_fixed, d_out_float, static_cast<hipStream_t>(hip_stream), 1, 0, false,
-               d_out_conf);
+    return compute_device(h, dsx::CALL_COMPUTE, 1, dL, dR, 0, H, W, stride_bytes, d_out_fixed, d_out_float, d_out_conf,
+                          hip_stream);
 }
 
 int dsx_postprocess_fast_device(const void *d_disp, int32_t H, int32_t W, int64_t in_pitch, int32_t crop,
@@ -1233,19 +1175,12 @@ int dsx_postprocess_fast_device(const void *d_disp, int32_t H, int32_t W, int64_
     if (H <= 0 || W <= 0 || in_pitch < W) return fail(DSX_EINVAL, "bad shape / pitch");
     if (crop < 0) return fail(DSX_EINVAL, "crop must be >= 0");
     if (crop >= W || (!d_out_disp && !d_out_depth)) return DSX_OK;  // empty result, as disp[:, crop:] is
+    dsx_post_params pp{};
+    pp.focal_length = focal_length, pp.baseline = baseline, pp.doffs = doffs, pp.eps = eps, pp.max_depth = max_depth;
+    pp.has_depth = 1, pp.has_max_depth = has_max_depth;
     dsx::PostArgs a{};
     a.disp = static_cast<const float *>(d_disp);
-    a.in_pitch = in_pitch;
-    a.H = H;
-    a.W = W;
-    a.crop = crop;
-    a.out_disp = static_cast<float *>(d_out_disp);
-    a.out_depth = static_cast<float *>(d_out_depth);
-    a.fB = (float)(focal_length * baseline);
-    a.doffs = (float)doffs;
-    a.eps = (float)eps;
-    a.max_depth = (float)max_depth;
-    a.has_max = has_max_depth ? 1 : 0;
+    post_args(a, pp, in_pitch, H, W, crop, d_out_disp, d_out_depth);
     DSX_HIP(dsx::launch_post_fast(a, static_cast<hipStream_t>(hip_stream)));
     return DSX_OK;
 }
@@ -1268,6 +1203,16 @@ int dsx_postprocess_full_device(const void *d_disp, int32_t H, int32_t W, int64_
 }
 
 namespace {
+// fill_method / fill_radius of the full chain (post_full_standalone, dsx_process_pair_device)
+int check_fill(int32_t fill_method, int32_t fill_radius) {
+    if (fill_radius < 0) return fail(DSX_EINVAL, "fill_radius must be >= 0");
+    if (fill_method != DSX_FILL_INPAINT && fill_method != DSX_FILL_NEAREST)
+        return fail(DSX_EINVAL, "fill_method must be DSX_FILL_INPAINT or DSX_FILL_NEAREST");
+    if (fill_method == DSX_FILL_NEAREST && fill_radius > dsx::kNearestMaxK)
+        return fail(DSX_EINVAL, "fill_method 'nearest': kernel_size (fill_radius) must be in [0, 31]");
+    return DSX_OK;
+}
+
 int check_refine(const dsx_refine *rf) {
     if (!rf) return fail(DSX_EINVAL, "NULL refine");
     if (rf->type == DSX_REFINE_NONE) return DSX_OK;
@@ -1298,53 +1243,27 @@ int refine_args(const dsx_refine *rf, const void *d_guide, int64_t guide_stride_
 
 // the stand-alone chain behind dsx_postprocess_full_ex_device and dsx_postprocess_device
 int post_full_standalone(const void *d_disp, int32_t H, int32_t W, int64_t in_pitch, int32_t crop,
-                         int32_t max_speckle_size, double max_diff, int32_t apply_outlier_removal,
-                         double outlier_threshold, int32_t outlier_kernel, int32_t fill_radius, int32_t fill_method,
-                         const dsx::InpaintOpts &fill_opts, void *d_out_disp, void *d_out_depth, double focal_length,
-                         double baseline, double doffs, double eps, double max_depth, int32_t has_max_depth,
-                         void *d_workspace, size_t workspace_bytes, void *hip_stream, const dsx_refine *rf = nullptr,
+                         const dsx_post_params &pp, void *d_out_disp, void *d_out_depth, void *d_workspace,
+                         size_t workspace_bytes, void *hip_stream, const dsx_refine *rf = nullptr,
                          const void *d_guide = nullptr, int64_t guide_stride_bytes = 0) {
-    g_err.clear();
-    if (fill_radius < 0) return fail(DSX_EINVAL, "fill_radius must be >= 0");
-    if (fill_method != DSX_FILL_INPAINT && fill_method != DSX_FILL_NEAREST)
-        return fail(DSX_EINVAL, "fill_method must be DSX_FILL_INPAINT or DSX_FILL_NEAREST");
-    if (fill_method == DSX_FILL_NEAREST && fill_radius > dsx::kNearestMaxK)
-        return fail(DSX_EINVAL, "fill_method 'nearest': kernel_size (fill_radius) must be in [0, 31]");
+    if (int rc = check_fill(pp.fill_method, pp.fill_radius)) return rc;
     if (!d_disp) return fail(DSX_EINVAL, "d_disp is NULL");
     if (H <= 0 || W <= 0 || in_pitch < W || crop < 0) return fail(DSX_EINVAL, "bad shape / pitch / crop");
-    if (outlier_kernel < 1 || (outlier_kernel & 1) == 0) return fail(DSX_EINVAL, "outlier_kernel must be odd");
+    if (pp.outlier_kernel < 1 || (pp.outlier_kernel & 1) == 0) return fail(DSX_EINVAL, "outlier_kernel must be odd");
     dsx::RefineArgs ra{};
     if (int rc = refine_args(rf, d_guide, guide_stride_bytes, W, ra)) return rc;
-    if (crop >= W || (!d_out_disp && !d_out_depth)) return DSX_OK;
+    if (crop >= W || (!d_out_disp && !(pp.has_depth && d_out_depth))) return DSX_OK;
     if (!d_workspace || workspace_bytes < dsx::post_full_workspace(H, W, crop))
         return fail(DSX_EINVAL, "workspace too small (dsx_postprocess_workspace_bytes)");
     if ((int64_t)H * (W - crop) > 0x7FFFFFFF) return fail(DSX_EINVAL, "image too large for int32 labels");
-    if (fill_radius > 0 && fill_method == DSX_FILL_INPAINT) {
+    if (pp.fill_radius > 0 && pp.fill_method == DSX_FILL_INPAINT) {
         int rc = check_fill_shape(H, W - crop);
         if (!rc) rc = sticky_inpaint_timeout(d_workspace);
         if (rc) return rc;
     }
     dsx::PostFullArgs a{};
     a.disp = static_cast<const float *>(d_disp);
-    a.in_pitch = in_pitch;
-    a.H = H;
-    a.W = W;
-    a.crop = crop;
-    a.max_speckle = max_speckle_size;
-    a.max_diff16 = (int)(max_diff * 16);  // int(max_diff * 16), postprocess.py:30
-    a.apply_outliers = apply_outlier_removal ? 1 : 0;
-    a.kernel = outlier_kernel;
-    a.thr = (float)outlier_threshold;
-    a.out_disp = static_cast<float *>(d_out_disp);
-    a.out_depth = static_cast<float *>(d_out_depth);
-    a.fB = (float)(focal_length * baseline);
-    a.doffs = (float)doffs;
-    a.eps = (float)eps;
-    a.max_depth = (float)max_depth;
-    a.has_max = has_max_depth ? 1 : 0;
-    a.fill_radius = fill_radius;
-    a.fill_method = fill_method;
-    a.fill_opts = fill_opts;
+    post_full_args(a, pp, in_pitch, H, W, crop, d_out_disp, d_out_depth);
     DSX_HIP(dsx::launch_post_full(a, d_workspace, static_cast<hipStream_t>(hip_stream), nullptr, &ra));
     return DSX_OK;
 }
@@ -1356,10 +1275,12 @@ int dsx_postprocess_full_ex_device(const void *d_disp, int32_t H, int32_t W, int
                                    void *d_out_disp, void *d_out_depth, double focal_length, double baseline,
                                    double doffs, double eps, double max_depth, int32_t has_max_depth,
                                    void *d_workspace, size_t workspace_bytes, void *hip_stream) {
-    return post_full_standalone(d_disp, H, W, in_pitch, crop, max_speckle_size, max_diff, apply_outlier_removal,
-                                outlier_threshold, outlier_kernel, fill_radius, DSX_FILL_INPAINT, dsx::InpaintOpts{},
-                                d_out_disp, d_out_depth, focal_length, baseline, doffs, eps, max_depth, has_max_depth,
-                                d_workspace, workspace_bytes, hip_stream);
+    g_err.clear();
+    // in declaration order; has_depth 1, and the rest 0: Telea's march with its default launch options
+    const dsx_post_params pp{max_diff, outlier_threshold, focal_length, baseline, doffs, eps, max_depth, DSX_POST_FULL,
+                             max_speckle_size, apply_outlier_removal, outlier_kernel, fill_radius, 1, has_max_depth};
+    return post_full_standalone(d_disp, H, W, in_pitch, crop, pp, d_out_disp, d_out_depth, d_workspace, workspace_bytes,
+                                hip_stream);
 }
 
 int dsx_postprocess_device(const void *d_disp, int32_t H, int32_t W, int64_t in_pitch, int32_t crop,
@@ -1376,14 +1297,8 @@ int dsx_postprocess_refine_device(const void *d_disp, int32_t H, int32_t W, int6
     g_err.clear();
     if (!pp) return fail(DSX_EINVAL, "NULL post parameters");
     if (pp->mode != DSX_POST_FULL) return fail(DSX_EINVAL, "dsx_postprocess_device runs mode DSX_POST_FULL");
-    dsx::InpaintOpts fo;
-    fo.spin_limit = pp->fill_spin_limit;
-    fo.steps = pp->fill_steps == 0 ? -1 : std::max(0, (int)pp->fill_steps);
-    return post_full_standalone(d_disp, H, W, in_pitch, crop, pp->max_speckle_size, pp->max_diff,
-                                pp->apply_outlier_removal, pp->outlier_threshold, pp->outlier_kernel, pp->fill_radius,
-                                pp->fill_method, fo, d_out_disp, pp->has_depth ? d_out_depth : nullptr,
-                                pp->focal_length, pp->baseline, pp->doffs, pp->eps, pp->max_depth, pp->has_max_depth,
-                                d_workspace, workspace_bytes, hip_stream, rf, d_guide, guide_stride_bytes);
+    return post_full_standalone(d_disp, H, W, in_pitch, crop, *pp, d_out_disp, d_out_depth, d_workspace,
+                                workspace_bytes, hip_stream, rf, d_guide, guide_stride_bytes);
 }
 
 void dsx_default_refine(dsx_refine *rf) {
@@ -1479,7 +1394,7 @@ int dsx_fill_holes_ex_device(const void *d_disp, int32_t H, int32_t W, int64_t i
     dsx::InpaintOpts o;
     if (opts) {
         o.spin_limit = opts->spin_limit;
-        o.steps = opts->steps == 0 ? -1 : std::max(0, (int)opts->steps);
+        o.steps = fill_steps(opts->steps);
     }
     DSX_HIP(dsx::launch_inpaint(static_cast<const float *>(d_disp), in_pitch, H, W, radius, static_cast<float *>(d_out),
                                 d_workspace, static_cast<hipStream_t>(hip_stream), o));
@@ -1552,22 +1467,8 @@ int dsx_resize_area_device(const void *d_img, int32_t Hs, int32_t Ws, int64_t st
 int dsx_compute_batch_device(dsx_handle *h, int32_t nframes, const void *dL, const void *dR, int64_t frame_stride_bytes,
                              int32_t H, int32_t W, int64_t stride_bytes, void *d_out_fixed, void *d_out_float,
                              void *hip_stream) {
-    g_err.clear();
-    if (!h) return fail(DSX_EINVAL, "handle is NULL");
-    if (!dL || !dR) return fail(DSX_EINVAL, "input pointers are NULL");
-    if (!d_out_fixed && !d_out_float) return fail(DSX_EINVAL, "at least one output is required");
-    if (nframes < 1) return fail(DSX_EINVAL, "nframes must be >= 1");
-    int rc = check_shape(H, W, stride_bytes);
-    if (rc) return rc;
-    if (nframes > 1 && frame_stride_bytes < (int64_t)(H - 1) * stride_bytes + W)
-        return fail(DSX_EINVAL, "frame_stride_bytes smaller than one frame");
-    if ((int64_t)nframes * H * W > ((int64_t)1 << 31) - 1)
-        return fail(DSX_EINVAL, "nframes * H * W must stay below 2^31 pixels per launch");
-    DSX_HIP(hipSetDevice(h->device));
-    rc = ensure_buffers(h, H, W, false, nframes, conf_call(h, nullptr));
-    if (rc) return rc;
-    return run(h, dL, dR, H, W, stride_bytes, d_out_fixed, d_out_float, static_cast<hipStream_t>(hip_stream), nframes,
-               frame_stride_bytes);
+    return compute_device(h, dsx::CALL_BATCH, nframes, dL, dR, frame_stride_bytes, H, W, stride_bytes, d_out_fixed,
+                          d_out_float, nullptr, hip_stream);
 }
 
 int dsx_right_map_device(dsx_handle *h, const void *dL, const void *dR, int32_t H, int32_t W, int64_t stride_bytes,
@@ -1576,27 +1477,19 @@ int dsx_right_map_device(dsx_handle *h, const void *dL, const void *dR, int32_t 
     if (!h || !dL || !dR || !d_out_dR) return fail(DSX_EINVAL, "NULL argument");
     int rc = check_shape(H, W, stride_bytes);
     if (rc) return rc;
-    DSX_HIP(hipSetDevice(h->device));
-    rc = ensure_buffers(h, H, W, false);
-    if (rc) return rc;
-    return run_right_pass(h, dL, dR, H, W, stride_bytes, static_cast<int16_t *>(d_out_dR),
+    dsx::CallPlan pl;
+    if ((rc = begin_call(h, dsx::CALL_RIGHT_MAP, false, 1, H, W, pl))) return rc;
+    return run_right_pass(h, pl, dL, dR, H, W, stride_bytes, static_cast<int16_t *>(d_out_dR),
                           static_cast<hipStream_t>(hip_stream));
 }
 
 int dsx_compute_host(dsx_handle *h, const uint8_t *L, const uint8_t *R, int32_t H, int32_t W, int64_t stride_bytes,
                      int16_t *out_fixed, float *out_float) {
-    g_err.clear();
-    if (!h) return fail(DSX_EINVAL, "handle is NULL");
-    if (!L || !R || !out_fixed) return fail(DSX_EINVAL, "NULL argument (out_fixed is required)");
     return compute_host(h, L, R, H, W, stride_bytes, out_fixed, out_float, nullptr);
 }
 
 int dsx_compute_conf_host(dsx_handle *h, const uint8_t *L, const uint8_t *R, int32_t H, int32_t W, int64_t stride_bytes,
                           int16_t *out_fixed, float *out_float, uint8_t *out_conf) {
-    if (!out_conf) return dsx_compute_host(h, L, R, H, W, stride_bytes, out_fixed, out_float);
-    g_err.clear();
-    if (!h) return fail(DSX_EINVAL, "handle is NULL");
-    if (!L || !R) return fail(DSX_EINVAL, "input pointers are NULL");
     return compute_host(h, L, R, H, W, stride_bytes, out_fixed, out_float, out_conf);
 }
 
@@ -1662,11 +1555,7 @@ int dsx_process_pair_refine_device(dsx_handle *h, const void *dL, const void *dR
         return fail(DSX_EINVAL, "post mode must be DSX_POST_FAST or DSX_POST_FULL");
     if (pp->mode == DSX_POST_FULL) {
         if (pp->outlier_kernel < 1 || (pp->outlier_kernel & 1) == 0) return fail(DSX_EINVAL, "outlier_kernel must be odd");
-        if (pp->fill_radius < 0) return fail(DSX_EINVAL, "fill_radius must be >= 0");
-        if (pp->fill_method != DSX_FILL_INPAINT && pp->fill_method != DSX_FILL_NEAREST)
-            return fail(DSX_EINVAL, "fill_method must be DSX_FILL_INPAINT or DSX_FILL_NEAREST");
-        if (pp->fill_method == DSX_FILL_NEAREST && pp->fill_radius > dsx::kNearestMaxK)
-            return fail(DSX_EINVAL, "fill_method 'nearest': kernel_size (fill_radius) must be in [0, 31]");
+        if ((rc = check_fill(pp->fill_method, pp->fill_radius))) return rc;
     }
     if (h->p.float_mode != DSX_FLOAT_FIXED)
         return fail(DSX_EINVAL, "process_pair needs float_mode DSX_FLOAT_FIXED (stereo_core.py:232: fixed / 16)");
@@ -1676,55 +1565,33 @@ int dsx_process_pair_refine_device(dsx_handle *h, const void *dL, const void *dR
     if (pp->mode == DSX_POST_FULL && (rc = refine_args(rf, dL, stride_bytes, W, ra))) return rc;
     const int crop = std::max(0, h->p.num_disp);  // stereo_core.py:168 crops num_disp columns
     const int Wc = W - crop;
-    const bool depth = pp->has_depth != 0;
-    if (Wc <= 0 || (!d_out_disp && !(depth && d_out_depth))) return DSX_OK;  // disp[:, num_disp:] is empty
+    if (Wc <= 0 || (!d_out_disp && !(pp->has_depth && d_out_depth))) return DSX_OK;  // disp[:, num_disp:] is empty
     if (pp->mode == DSX_POST_FULL && pp->fill_radius > 0 && pp->fill_method == DSX_FILL_INPAINT) {
         rc = check_fill_shape(H, Wc);
         if (!rc) rc = sticky_inpaint_timeout(h);
         if (rc) return rc;
     }
-    DSX_HIP(hipSetDevice(h->device));
-    rc = ensure_buffers(h, H, W, false, 1, conf_call(h, nullptr));
-    if (rc) return rc;
-    const size_t n = (size_t)H * W;
     const bool full = pp->mode == DSX_POST_FULL;
-    if (!full && (rc = grow(h->ppDisp, h->ppDispBytes, n * 4))) return rc;
-    if (full && (rc = grow(h->ppFixed, h->ppFixedBytes, n * 2))) return rc;
-    const size_t wsb = dsx::post_full_workspace(H, W, crop);
-    if (pp->mode == DSX_POST_FULL && h->ppWsBytes < wsb) {
-        (void)hipFree(h->ppWs);
-        h->ppWs = nullptr;
-        h->ppWsBytes = 0;
-        DSX_HIP(hipMalloc(&h->ppWs, wsb));
-        h->ppWsBytes = wsb;
-    }
+    dsx::CallPlan pl;
+    if ((rc = begin_call(h, full ? dsx::CALL_PAIR_FULL : dsx::CALL_PAIR_FAST, false, 1, H, W, pl))) return rc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    // the float map and the workspace are handle scratch: order after the previous call's use
-    if (h->scratchPending && h->scratchStream != st) DSX_HIP(hipStreamWaitEvent(st, h->scratchDone, 0));
+    // the matcher's map and the workspace are handle scratch: order after the previous call's use
+    if ((rc = wait_scratch(h, st))) return rc;
     ScratchRecord rec_(h, st, true);
-    const float fB = (float)(pp->focal_length * pp->baseline);
     dsx::PostFullArgs a{};
     bool defer = false;
     if (full) {
         // full mode reads the x16 map itself (postprocess.py:27 computes int16(d * 16) of d = fixed / 16,
         // which is `fixed` again): 2 B per pixel written by the matcher and read by the speckle pass
-        a.in16 = h->ppFixed;
-        a.in_pitch = W;
-        a.H = H;
-        a.W = W;
-        a.crop = crop;
-        a.max_speckle = pp->max_speckle_size;
-        a.kernel = pp->outlier_kernel;
-        // the fused pass's LR check moves into the speckle pass's loads (no lr_fixup launch) when that
-        // pass is the two-launch form and the matcher is the fused pass with a check
-        const bool fusedp = h->p.path == DSX_PATH_FUSED && !h->p.aggregation && !volume_only(h->p.cost) &&
-                            !h->p.sgbm_post && !conf_call(h, nullptr);  // a threshold: the volume path
-        const bool lrc = h->p.lr_form == DSX_LR_FORM_SGBM || h->p.disp12_max_diff >= 0;
-        // a texture threshold masks the checked map: the fix-up runs in run(), then the mask
-        defer = fusedp && lrc && dsx::post_full_two_launch(a) && h->pf.texture_threshold == 0 &&
-                getenv("DSX_NO_DEFER_LR") == nullptr;
+        a.in16 = h->ppFixed.as<int16_t>();
+        post_full_args(a, *pp, W, H, W, crop, d_out_disp, d_out_depth);
+        a.fill_opts.status_key = h;  // the handle's own timeout flag and step history
+        // the fused pass's LR check moves into the speckle pass's loads (no lr_fixup launch) when the plan
+        // allows it (a fused matcher with a check, no mask) and that pass is the two-launch form
+        defer = pl.defer_lr_ok && dsx::post_full_two_launch(a) && getenv("DSX_NO_DEFER_LR") == nullptr;
     }
-    rc = run(h, dL, dR, H, W, stride_bytes, full ? h->ppFixed : nullptr, full ? nullptr : h->ppDisp, st, 1, 0, defer);
+    rc = run(h, pl, dL, dR, H, W, stride_bytes, full ? h->ppFixed.ptr : nullptr, full ? nullptr : h->ppDisp.ptr, st, 0,
+             defer);
     if (rc) return rc;
     rec_.active = true;  // run() recorded its own event; this call's kernels continue below
     if (full) {
@@ -1736,40 +1603,15 @@ int dsx_process_pair_refine_device(dsx_handle *h, const void *dL, const void *dR
             a.lr_max = h->p.disp12_max_diff;
             a.lr_kshift = h->lastKshift;
         }
-        a.max_diff16 = (int)(pp->max_diff * 16);  // int(max_diff * 16), postprocess.py:30
-        a.apply_outliers = pp->apply_outlier_removal ? 1 : 0;
-        a.thr = (float)pp->outlier_threshold;
-        a.out_disp = static_cast<float *>(d_out_disp);
-        a.out_depth = depth ? static_cast<float *>(d_out_depth) : nullptr;
-        a.fB = fB;
-        a.doffs = (float)pp->doffs;
-        a.eps = (float)pp->eps;
-        a.max_depth = (float)pp->max_depth;
-        a.has_max = pp->has_max_depth ? 1 : 0;
-        a.fill_radius = pp->fill_radius;
-        a.fill_method = pp->fill_method;
-        a.fill_opts.status_key = h;  // the handle's own timeout flag and step history
-        a.fill_opts.spin_limit = pp->fill_spin_limit;
-        a.fill_opts.steps = pp->fill_steps == 0 ? -1 : std::max(0, (int)pp->fill_steps);
         TimingHook hook(h);
-        hipError_t e = dsx::launch_post_full(a, h->ppWs, st, h->p.timing ? &hook : nullptr, &ra);
+        hipError_t e = dsx::launch_post_full(a, h->ppWs.ptr, st, h->p.timing ? &hook : nullptr, &ra);
         if (e != hipSuccess) return fail(DSX_EHIP, std::string("post-processing launch: ") + hipGetErrorString(e));
         if (hook.rc) return hook.rc;
     } else {
-        dsx::PostArgs a{};
-        a.disp = h->ppDisp;
-        a.in_pitch = W;
-        a.H = H;
-        a.W = W;
-        a.crop = crop;
-        a.out_disp = static_cast<float *>(d_out_disp);
-        a.out_depth = depth ? static_cast<float *>(d_out_depth) : nullptr;
-        a.fB = fB;
-        a.doffs = (float)pp->doffs;
-        a.eps = (float)pp->eps;
-        a.max_depth = (float)pp->max_depth;
-        a.has_max = pp->has_max_depth ? 1 : 0;
-        DSX_LAUNCH(h, "median_depth", st, dsx::launch_post_fast(a, st));
+        dsx::PostArgs f{};
+        f.disp = h->ppDisp.as<float>();
+        post_args(f, *pp, W, H, W, crop, d_out_disp, d_out_depth);
+        DSX_LAUNCH(h, "median_depth", st, dsx::launch_post_fast(f, st));
     }
     return rec_.finish();
 }
@@ -1811,10 +1653,11 @@ int dsx_reset_times(dsx_handle *h) {
 }
 
 int dsx_workspace_bytes(dsx_handle *h, int64_t *bytes) {
+    g_err.clear();
     if (!h || !bytes) return fail(DSX_EINVAL, "NULL argument");
-    *bytes = (int64_t)(h->stagingBytes + h->dConfBytes + h->pfBytes + h->lrKeysBytes + h->dStarBytes + h->vol_bytes + h->btWsBytes + h->censusWsBytes +
-                       h->postInBytes + h->postWsBytes + h->sgmSBytes + h->sgmLBytes + h->ppDispBytes +
-                       h->ppFixedBytes + h->ppWsBytes);
+    size_t sum = 0;
+    for_each_buf(h, [&sum](const DevBuf &b) { sum += b.held; });
+    *bytes = (int64_t)sum;
     return DSX_OK;
 }
 

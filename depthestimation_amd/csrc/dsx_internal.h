@@ -3,20 +3,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dsx_plan.h"  // Geometry and the BM_* cost layouts
+
 namespace dsx {
 
 enum Side : int { SIDE_LEFT = 0, SIDE_RIGHT = 1, SIDE_VOLUME = 2, SIDE_LEFT_LR = 3 };
 
 constexpr int kVolThreads = 256;    // K2 (volume WTA) block size
-
-// Launch geometry derived from (num_disp, cost), see pick_geometry in dsx_api.hip.
-//   NW : waves per bm2 block;  Dp : padded disparity count
-//   TX, TPP : K2 (vol_wta) tile = 32-disparity slices, TPP = Dp / 32 lanes per pixel
-//   DB : key shift bits for K2's packed (cost << DB | d) keys
-struct Geometry {
-    int NW, Dp, TX, TPP, DB;
-    int kind;  // BM_SAD / BM_SSD / BM_SAD1 (the fused passes' cost layout)
-};
 
 // Arguments of the fused pass kernel bm2 (dsx_bm.hip).
 struct Bm2Args {
@@ -87,10 +80,8 @@ __device__ __forceinline__ int div_trunc_small(int num, int den2) {
     return q;
 }
 
-// nw = waves per block: SAD Dp = 128*nw (nw in {1,2,4}), SSD Dp = 64*nw (nw in {1,2,4,8}).
-// bm2 cost layouts: SAD disparity pairs (u16), SSD one disparity per lane (u32), SAD1 = SAD in the SSD
-// layout (u32 sums, one disparity per lane; fused passes with D <= 64, pick_geometry in dsx_api.hip)
-enum { BM_SAD = 0, BM_SSD = 1, BM_SAD1 = 2 };
+// nw = waves per block: SAD Dp = 128*nw (nw in {1,2,4}), SSD Dp = 64*nw (nw in {1,2,4,8}); kind: the BM_*
+// cost layout (pick_geometry in dsx_plan.h)
 hipError_t launch_bm2(int radius, int kind, int nw, const Bm2Args &a, hipStream_t st);
 hipError_t launch_volume_wta(int TX, bool ssd, const VolArgs &a, hipStream_t st);
 // LR check after the left pass: invalidate x where |dR(x - m - d*) - d*| > lr over `rows` rows

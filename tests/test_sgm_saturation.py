@@ -1,7 +1,7 @@
 """Preconditions of the saturated SGM parity tests (tests/test_gpu_sgm_edges.py), on the CPU.
 
 The concurrent SGM form stores L_r as u16 and is taken only while max cost + P2 < 65535
-(dsx_api.hip sgm_concurrent()).  Textured ``stereo_pair`` inputs leave L_r below a third of that
+(dsx_plan.h sgm_concurrent()).  Textured ``stereo_pair`` inputs leave L_r below a third of that
 bound (largest L_r of the older tests: 18,955 of 66,375), so the GPU tests use thresholded and striped
 inputs instead.  These tests assert with the oracle that those inputs really put L_r and the sums on
 the limits, so a later change of the generators cannot quietly turn the GPU tests back into easy
