@@ -10,6 +10,7 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 
 from .input import load_stereo_pair
+from .pointcloud import write_ply
 from .stereo_core import StereoCore
 
 
@@ -55,3 +56,16 @@ class StereoDepthEstimator:
         self.disparity_map = disparity_px
         self.depth_map = depth_m
         return disparity_px, depth_m
+
+    def point_cloud(self, colors=None):
+        """The last estimate as a point cloud (StereoCore.point_cloud): ``(points, colors, index)`` - float32
+        N x 3 metric XYZ of the valid pixels in row-major order, uint8 N x 3 RGB (from the left rectified
+        image unless ``colors`` is given), int32 N pixel indices into the disparity map.  An addition of this
+        build; needs 'focal_length' and 'baseline'."""
+        return self.core.point_cloud(colors=colors)
+
+    def save_point_cloud(self, path, colors=None) -> int:
+        """Write ``point_cloud()`` as a binary little-endian PLY (pointcloud.write_ply); returns the number of points."""
+        points, rgb, _ = self.point_cloud(colors=colors)
+        write_ply(path, points, rgb)
+        return len(points)

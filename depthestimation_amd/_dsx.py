@@ -46,6 +46,7 @@ EXPORTS = (
     "dsx_postprocess_refine_device", "dsx_process_pair_refine_device",
     "dsx_default_confidence", "dsx_check_confidence", "dsx_set_confidence", "dsx_compute_conf_device",
     "dsx_compute_conf_host",
+    "dsx_check_cloud", "dsx_reproject_device", "dsx_point_cloud_workspace_bytes", "dsx_point_cloud_device",
 )
 
 
@@ -118,6 +119,25 @@ class DsxRefine(ctypes.Structure):
     ]
 
 
+CLOUD_TILE = 2048  # DSX_CLOUD_TILE: pixels per block of the point-cloud compaction
+
+
+class DsxCloud(ctypes.Structure):
+    """dsx_cloud (include/dsx.h): the reprojection of a disparity map to XYZ."""
+    _fields_ = [
+        ("focal_length", ctypes.c_double),
+        ("baseline", ctypes.c_double),
+        ("cx", ctypes.c_float),
+        ("cy", ctypes.c_float),
+        ("doffs", ctypes.c_float),
+        ("eps", ctypes.c_float),
+        ("max_depth", ctypes.c_float),
+        ("has_max_depth", ctypes.c_int32),
+        ("x0", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
 POST_MODE = {"fast": 1, "full": 2}  # DSX_POST_* (include/dsx.h)
 FILL_METHOD = {"inpaint": 0, "nearest": 1}  # DSX_FILL_* (fill_holes' method names, postprocess.py:72-118)
 NEAREST_PATH = {"auto": 0, "fused": 1, "stepwise": 2}  # DSX_NEAREST_*
@@ -168,7 +188,13 @@ def _bind(lib):
     RF = ctypes.POINTER(DsxRefine)
     CF = ctypes.POINTER(DsxConfidence)
     PP = ctypes.POINTER(DsxPostParams)
+    CL = ctypes.POINTER(DsxCloud)
     sig = {
+        "dsx_check_cloud": (ctypes.c_int, [CL]),
+        "dsx_reproject_device": (ctypes.c_int, [vp, i32, i32, i64, CL, vp, vp]),
+        "dsx_point_cloud_workspace_bytes": (i64, [i32, i32]),
+        "dsx_point_cloud_device": (ctypes.c_int, [vp, i32, i32, i64, CL, vp, i64, i32, vp, vp, vp, i64, vp, vp, i64,
+                                                   vp]),
         "dsx_default_confidence": (None, [CF]),
         "dsx_check_confidence": (ctypes.c_int, [P, CF]),
         "dsx_set_confidence": (ctypes.c_int, [vp, CF]),
@@ -368,6 +394,22 @@ def make_refine(refine="none", refine_radius=5, refine_sigma=8, refine_fill=True
     rf.fill = int(bool(refine_fill))
     check(lib().dsx_check_refine(ctypes.byref(rf)), "dsx_check_refine")
     return rf
+
+
+def make_cloud(focal_length, baseline, cx, cy, doffs=0.0, eps=1e-6, max_depth=None, x0=0) -> DsxCloud:
+    """dsx_cloud from the reprojection keywords; ValueError for a value dsx_check_cloud refuses."""
+    if focal_length is None or baseline is None:
+        raise ValueError("a point cloud needs focal_length and baseline")
+    if isinstance(x0, bool) or int(x0) != x0:
+        raise ValueError("x0 must be an integer >= 0")
+    c = DsxCloud()
+    c.focal_length, c.baseline, c.cx, c.cy = float(focal_length), float(baseline), float(cx), float(cy)
+    c.doffs, c.eps = float(doffs or 0.0), float(eps)
+    c.max_depth = float(max_depth) if max_depth is not None else 0.0
+    c.has_max_depth = int(max_depth is not None)
+    c.x0 = int(x0)
+    check(lib().dsx_check_cloud(ctypes.byref(c)), "dsx_check_cloud")
+    return c
 
 
 def check_prefilter(p, f: DsxPrefilter) -> None:

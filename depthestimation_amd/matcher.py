@@ -678,6 +678,124 @@ def wmedian_device(disp, guide, radius=5, sigma=8, fill=True, out=None, stream=N
     return out
 
 
+def _cloud_args(disp, focal_length, baseline, principal_point, doffs, eps, max_depth, x0):
+    """The checks the two point-cloud calls share: (H, W, dsx_cloud)."""
+    import torch
+
+    if not hasattr(disp, "dtype") or disp.dtype != torch.float32 or disp.dim() != 2 or not disp.is_cuda or \
+            (disp.shape[1] > 1 and disp.stride(1) != 1):
+        raise ValueError("disp must be a float32 H x W device tensor with unit column stride")
+    H, W = disp.shape
+    if isinstance(x0, bool) or int(x0) != x0 or int(x0) < 0:
+        raise ValueError("x0 must be an integer >= 0")
+    if principal_point is None:
+        cx, cy = (int(x0) + W - 1) / 2.0, (H - 1) / 2.0  # the centre of the uncropped image
+    else:
+        cx, cy = principal_point
+    return H, W, _dsx.make_cloud(focal_length, baseline, cx, cy, doffs, eps, max_depth, x0)
+
+
+def reproject_device(disp, focal_length, baseline, principal_point=None, doffs=0.0, eps=1e-6, max_depth=None, x0=0,
+                     out=None, stream=None):
+    """The organized cloud on the device (dsx_reproject_device; host restatement
+    pointcloud.reproject_disparity, equal bit for bit): float32 H x W disparity tensor (unit column stride, any
+    row stride) whose column 0 is image column ``x0`` -> contiguous float32 H x W x 3, NaN at invalid pixels.
+    ``principal_point``: (cx, cy) in uncropped image coordinates, None for the image centre.  One launch,
+    asynchronous on ``stream``."""
+    import torch
+
+    H, W, c = _cloud_args(disp, focal_length, baseline, principal_point, doffs, eps, max_depth, x0)
+    if out is None:
+        out = torch.empty((H, W, 3), dtype=torch.float32, device=disp.device)
+    elif out.shape != (H, W, 3) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != disp.device:
+        raise ValueError("out must be a contiguous float32 H x W x 3 tensor on the input's device")
+    if H == 0 or W == 0:
+        return out
+    rc = _dsx.lib().dsx_reproject_device(disp.data_ptr(), H, W, max(disp.stride(0), W), ctypes.byref(c),
+                                         out.data_ptr(), _stream_ptr(stream))
+    _dsx.check(rc, "dsx_reproject_device")
+    return out
+
+
+def point_cloud_device(disp, focal_length, baseline, principal_point=None, doffs=0.0, eps=1e-6, max_depth=None, x0=0,
+                       colors=None, capacity=None, out_points=None, out_colors=None, out_index=None, stream=None,
+                       sync=True):
+    """The compact cloud on the device (dsx_point_cloud_device; host restatement pointcloud.point_cloud, equal
+    bit for bit, count and order included): the valid points of ``disp`` in row-major pixel order.
+
+    ``disp``: float32 H x W HIP tensor (unit column stride, any row stride) whose column 0 is image column
+    ``x0``.  ``colors``: the UNCROPPED uint8 image on the same device, H x (x0 + W) x 3 BGR or H x (x0 + W) gray
+    (packed pixels, any row stride or offset), read from column ``x0`` on; None: no colours.  ``capacity``: room
+    in the outputs, in points (None: H * W); ``out_points`` (float32 capacity x 3), ``out_colors`` (uint8
+    capacity x 3) and ``out_index`` (int32 capacity) may be the caller's; ``out_index=False`` writes no index
+    (d_index NULL) and returns None in its place.
+
+    ``sync=True`` waits, reads the count N and returns ``(points[:N], colors[:N] or None, index[:N])``;
+    ValueError when N exceeds the capacity.  ``sync=False`` never touches the host: it returns the
+    full-capacity tensors and the int32 count tensor ``(points, colors or None, index, count)``; the count is
+    always the true N, only the first ``capacity`` points are written.  Three launches on ``stream``.
+
+    Stream order: the outputs and the count are allocated on torch's current stream and written on ``stream``
+    (only the workspace is marked with ``record_stream``), as in ``wmedian_device``.  With ``sync=False`` on a
+    stream other than torch's current one the caller orders its later use of the returned tensors after
+    ``stream`` (an event, ``wait_stream``) and keeps them alive until it has finished."""
+    import torch
+
+    H, W, c = _cloud_args(disp, focal_length, baseline, principal_point, doffs, eps, max_depth, x0)
+    dev = disp.device
+    if capacity is None:
+        capacity = H * W
+    if isinstance(capacity, bool) or int(capacity) != capacity or int(capacity) < 0:
+        raise ValueError("capacity must be an integer >= 0")
+    cap = int(capacity)
+    ch = 0
+    if colors is not None:
+        ok = hasattr(colors, "dtype") and colors.dtype == torch.uint8 and colors.device == dev and \
+            colors.dim() in (2, 3) and tuple(colors.shape[:2]) == (H, c.x0 + W)
+        if ok and colors.dim() == 3:
+            ok = colors.shape[2] == 3 and colors.stride(2) == 1 and colors.stride(1) == 3
+        elif ok:
+            ok = colors.shape[1] <= 1 or colors.stride(1) == 1
+        if not ok:
+            raise ValueError("colors must be a uint8 H x (x0 + W) gray or H x (x0 + W) x 3 BGR tensor on disp's "
+                             "device with packed pixels")
+        ch = 3 if colors.dim() == 3 else 1
+
+    def own(t, shape, dtype, name):
+        if t is None:
+            return torch.empty(shape, dtype=dtype, device=dev)
+        if not hasattr(t, "data_ptr") or t.shape != shape or t.dtype != dtype or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{name} must be a contiguous {str(dtype).split('.')[-1]} tensor of shape {tuple(shape)} "
+                             "on the input's device")
+        return t
+
+    points = own(out_points, (cap, 3), torch.float32, "out_points")
+    cols = own(out_colors, (cap, 3), torch.uint8, "out_colors") if ch else None
+    index = None if out_index is False else own(out_index, (cap,), torch.int32, "out_index")
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    L = _dsx.lib()
+    nbytes = int(L.dsx_point_cloud_workspace_bytes(H, W))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    rc = L.dsx_point_cloud_device(disp.data_ptr() if H and W else None, H, W, max(disp.stride(0), W), ctypes.byref(c),
+                                  colors.data_ptr() if ch and H and W else None,
+                                  max(colors.stride(0), (c.x0 + W) * ch) if ch else 0, ch,
+                                  points.data_ptr() if cap else None, cols.data_ptr() if ch and cap else None,
+                                  index.data_ptr() if cap and index is not None else None, cap, count.data_ptr(),
+                                  None if ws is None else ws.data_ptr(), nbytes, _stream_ptr(stream))
+    _dsx.check(rc, "dsx_point_cloud_device")
+    if ws is not None:
+        _keep_until_done(ws, stream)
+    if not sync:
+        return points, cols, index, count
+    if stream is not None:
+        st = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(stream), device=dev)
+        st.synchronize()
+    n = int(count.item())
+    if n > cap:
+        raise ValueError(f"the cloud has {n} points but the outputs have room for {cap} (capacity)")
+    return points[:n], None if cols is None else cols[:n], None if index is None else index[:n]
+
+
 def fill_holes_status(workspace=None):
     """Raise RuntimeError if a hole-filling march timed out since the last check (its remaining
     holes were left unfilled); the condition is cleared.  ``workspace``: a ``FillWorkspace`` (its

@@ -342,6 +342,26 @@ class RectificationCache:
 def compute_maps(cam_matrix_L, cam_matrix_R, baseline, image_width, image_height, dist_coeff_L=None,
                  dist_coeff_R=None, rotation=None, translation=None, alpha=0.0) -> Dict[str, np.ndarray]:
     """rectify.py:53-78 / 189-227: stereoRectify + both undistort-rectify maps."""
+    K1, D1, K2, D2, size, (R1, R2, P1, P2, _) = _stereo_rectify_for(
+        cam_matrix_L, cam_matrix_R, baseline, image_width, image_height, dist_coeff_L, dist_coeff_R, rotation,
+        translation, alpha)
+    m1L, m2L = init_undistort_rectify_map(K1, D1, R1, P1, size)
+    m1R, m2R = init_undistort_rectify_map(K2, D2, R2, P2, size)
+    return {'map1_L': m1L, 'map2_L': m2L, 'map1_R': m1R, 'map2_R': m2R}
+
+
+def rectified_principal_point(cam_matrix_L, cam_matrix_R, baseline, image_width, image_height, dist_coeff_L=None,
+                              dist_coeff_R=None, rotation=None, translation=None, alpha=0.0) -> Tuple[float, float]:
+    """(cx, cy) of the left rectified image: (P1[0, 2], P1[1, 2]) of the stereo_rectify call behind
+    ``compute_maps`` for the same arguments (the point-cloud output's principal point)."""
+    P1 = _stereo_rectify_for(cam_matrix_L, cam_matrix_R, baseline, image_width, image_height, dist_coeff_L,
+                             dist_coeff_R, rotation, translation, alpha)[5][2]
+    return float(P1[0, 2]), float(P1[1, 2])
+
+
+def _stereo_rectify_for(cam_matrix_L, cam_matrix_R, baseline, image_width, image_height, dist_coeff_L, dist_coeff_R,
+                        rotation, translation, alpha):
+    """compute_maps' arguments as stereo_rectify takes them, and its result: (K1, D1, K2, D2, size, result)."""
     K1 = np.asarray(cam_matrix_L, np.float64)
     K2 = np.asarray(cam_matrix_R, np.float64)
     D1 = np.asarray(dist_coeff_L, np.float64) if dist_coeff_L is not None else np.zeros(5)
@@ -349,10 +369,7 @@ def compute_maps(cam_matrix_L, cam_matrix_R, baseline, image_width, image_height
     size = (int(image_width), int(image_height))
     R = np.asarray(rotation, np.float64) if rotation is not None else np.eye(3)
     T = np.asarray(translation, np.float64) if translation is not None else np.array([-baseline, 0.0, 0.0])
-    R1, R2, P1, P2, _ = stereo_rectify(K1, D1, K2, D2, size, R, T, zero_disparity=True, alpha=alpha)
-    m1L, m2L = init_undistort_rectify_map(K1, D1, R1, P1, size)
-    m1R, m2R = init_undistort_rectify_map(K2, D2, R2, P2, size)
-    return {'map1_L': m1L, 'map2_L': m2L, 'map1_R': m1R, 'map2_R': m2R}
+    return K1, D1, K2, D2, size, stereo_rectify(K1, D1, K2, D2, size, R, T, zero_disparity=True, alpha=alpha)
 
 
 def _ensure_image_size(image: np.ndarray, size: Tuple[int, int]) -> np.ndarray:

@@ -60,6 +60,10 @@ Keys added to ``sgbm_params`` (accepted by ``configure_sgbm`` like the reference
   'confidence_threshold': int         (0 = off; t in 1..255: pixels of confidence below t become invalid
                                        after the LR check, before the texture mask and 'sgbm_post' - holes
                                        for the fillers and 'refine' to close from trusted neighbours)
+  'principal_point': (cx, cy) | None  (None.  The principal point of the left rectified image in uncropped
+                                       pixel coordinates, scaled by downscale_factor like 'focal_length'; used
+                                       by ``point_cloud`` (pointcloud.py: disparity -> XYZ + RGB).  None: with
+                                       a full calibration the rectification's own P1, else the image centre)
 Keys of the reference that have no block-matching meaning are kept, validated and reported
 but do not change the result: 'prefilter_cap' unless 'cost' is 'bt' or a prefilter is set, 'speckle_window_size' /
 'speckle_range' unless 'sgbm_post' is set, and 'sgbm_mode' / P1 / P2 while 'aggregation' is 'none'
@@ -76,11 +80,21 @@ import numpy as np
 
 from .input import resize_area, resize_area_device
 from .matcher import (HipBlockMatcher, default_workspace, fill_holes_status, postprocess_fast_device,
-                      postprocess_full_device, rectify_device)
+                      point_cloud_device, postprocess_full_device, rectify_device)
+from .pointcloud import point_cloud as host_point_cloud
 from .postprocess import median_blur3, postprocess_disparity
-from .rectify import RectificationCache, rectify_images, to_grayscale_bgr
+from .rectify import RectificationCache, rectified_principal_point, rectify_images, to_grayscale_bgr
 
 _SGBM_MODES = ("sgbm", "hh", "sgbm_3way", "hh4")
+_CALIBRATION_KEYS = ('cam_matrix_L', 'cam_matrix_R', 'baseline', 'image_width', 'image_height')
+
+
+def _valid_principal_point(pp) -> bool:
+    """Two finite numbers (cx, cy)."""
+    try:
+        return len(pp) == 2 and all(not isinstance(v, (bool, np.bool_)) and np.isfinite(float(v)) for v in pp)
+    except (TypeError, ValueError):
+        return False
 
 
 class _HostView:
@@ -166,7 +180,9 @@ class StereoCore:
             'refine_fill': True,
             'confidence': False,
             'confidence_threshold': 0,
+            'principal_point': None,
         }
+        self._pp_cache = None  # (calibration key, (cx, cy) of the left rectified image)
         self.confidence_map = None
         self._build_sgbm()
         self.disparity_map = None
@@ -194,6 +210,8 @@ class StereoCore:
         if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, float, np.integer, np.floating)) or \
                 int(t) != t or not 0 <= int(t) <= 255:
             raise ValueError("Invalid parameter value for 'confidence_threshold': expected an integer in [0, 255]")
+        if p.get('principal_point') is not None and not _valid_principal_point(p['principal_point']):
+            raise ValueError("Invalid parameter value for 'principal_point': expected None or two finite numbers")
         self.P1 = 8 * p['block_size'] ** 2
         self.P2 = 32 * p['block_size'] ** 2
         self.mode = p.get('sgbm_mode', 'sgbm_3way') if p.get('sgbm_mode') in _SGBM_MODES else 'sgbm_3way'
@@ -236,6 +254,8 @@ class StereoCore:
             kwargs['focal_length'] = kwargs['focal_length'] * self.downscale_factor
         if 'doffs' in kwargs:
             kwargs['doffs'] = kwargs['doffs'] * self.downscale_factor
+        if _valid_principal_point(kwargs.get('principal_point')):  # anything else: _build_sgbm refuses it
+            kwargs['principal_point'] = tuple(float(v) * self.downscale_factor for v in kwargs['principal_point'])
         self.sgbm_params.update(kwargs)
         self._build_sgbm()
 
@@ -426,6 +446,97 @@ class StereoCore:
         if max_depth is not None:
             Z[Z > max_depth] = max_depth
         return Z
+
+    # -- point cloud ---------------------------------------------------------------------
+    def resolve_principal_point(self, height: int, width: int) -> Tuple[float, float]:
+        """(cx, cy) of the left rectified image, ``height`` x ``width`` uncropped: the 'principal_point' key;
+        else, with a full calibration, (P1[0, 2], P1[1, 2]) of the stereo_rectify call behind the
+        rectification maps (computed once per calibration); else the image centre."""
+        p = self.sgbm_params
+        if p.get('principal_point') is not None:
+            cx, cy = p['principal_point']
+            return float(cx), float(cy)
+        if all(p.get(k) is not None for k in _CALIBRATION_KEYS):
+            args = (p['cam_matrix_L'], p['cam_matrix_R'], p['baseline'], p['image_width'], p['image_height'],
+                    p.get('dist_coeff_L'), p.get('dist_coeff_R'), p.get('rotation'), p.get('translation'), 1.0)
+            key = self._rect_cache._make_key(*args)
+            if self._pp_cache is None or self._pp_cache[0] != key:
+                self._pp_cache = (key, rectified_principal_point(*args))
+            return self._pp_cache[1]
+        return (width - 1) / 2.0, (height - 1) / 2.0
+
+    def _cloud_kwargs(self, height: int, width: int) -> dict:
+        """The reprojection of a cropped ``height`` x ``width`` map of this core, as the depth call passes it:
+        x0 = num_disp, eps = min_disp; focal length, baseline, doffs and max_depth from the params."""
+        p = self.sgbm_params
+        f, B = p.get('focal_length'), p.get('baseline')
+        if f is None or B is None:
+            raise ValueError("A point cloud needs 'focal_length' and 'baseline' (configure_sgbm).")
+        x0 = int(p['num_disp'])
+        return dict(focal_length=f, baseline=B, principal_point=self.resolve_principal_point(height, x0 + width),
+                    doffs=p.get('doffs', 0.0), eps=p.get('min_disp', 5.0), max_depth=p.get('max_depth'), x0=x0)
+
+    def point_cloud(self, colors=None):
+        """The last frame's ``disparity_map`` as a point cloud: ``(points, colors, index)`` host arrays -
+        float32 N x 3 metric XYZ (x right, y down, z forward) of the valid pixels in row-major order, uint8
+        N x 3 RGB, int32 N ``y * W + x`` into the cropped map (to gather ``confidence_map`` or anything else).
+        ``colors``: an uncropped uint8 image, H x W_full x 3 BGR or H x W_full gray; None: ``left_rectified``.
+        The device compacts the cloud (matcher.point_cloud_device) when the matcher has not been replaced
+        (no ``compute_disparity`` override) and a HIP device is there - a rule of its own, looser than
+        ``_device_pipeline_ok``: the map is a finished host array whatever produced it.  Otherwise the host
+        restatement (pointcloud.point_cloud) runs; the arrays are the same either way.  This path is not
+        device-resident: the host ``disparity_map`` that ``estimate_depth`` copied back is uploaded again and
+        the cloud comes back over PCIe (only the rectified left image of a device frame is reused in HBM).
+        Callers that keep frames on the device use ``point_cloud_device``."""
+        disp = self.disparity_map
+        if disp is None:
+            raise ValueError("No frame has been processed: call estimate_depth first.")
+        disp = np.asarray(disp, np.float32)
+        H, W = disp.shape
+        kw = self._cloud_kwargs(H, W)
+        on_device = 'compute_disparity' not in self.__dict__ and self._torch_device_ok()
+        if colors is None:
+            left = self.__dict__.get("_left_rect")
+            # the device pipeline's rectified image is still in HBM: no copy back just to send it again
+            colors = left.t if on_device and isinstance(left, _HostView) else self.left_rectified
+        if colors is not None and not hasattr(colors, "is_cuda"):
+            colors = np.asarray(colors)
+        if colors is not None and tuple(colors.shape[:2]) != (H, kw['x0'] + W):
+            raise ValueError("colors must be a uint8 image of the uncropped frame's size")
+        if not on_device:
+            if hasattr(colors, "is_cuda"):
+                colors = colors.cpu().numpy()
+            return host_point_cloud(disp, colors=colors, **kw)
+        import torch
+        dev = torch.device("cuda", int(self.sgbm_params.get('device', 0)))
+        if colors is not None:
+            colors = colors.to(dev) if hasattr(colors, "is_cuda") else torch.from_numpy(np.ascontiguousarray(colors)).to(dev)
+        pts, col, idx = point_cloud_device(torch.from_numpy(np.ascontiguousarray(disp)).to(dev), colors=colors, **kw)
+        return pts.cpu().numpy(), None if col is None else col.cpu().numpy(), idx.cpu().numpy()
+
+    def point_cloud_device(self, disp, colors=None, stream=None, sync=True):
+        """``point_cloud`` for the tensors of ``estimate_depth_device`` / ``process_pair_device``: ``disp`` the
+        cropped float32 disparity tensor, ``colors`` an uncropped uint8 tensor on its device (None: the
+        rectified left image of the last device frame, if it has the frame's size).  Returns what
+        matcher.point_cloud_device returns: with ``sync`` the exact-length tensors, without it the
+        full-capacity tensors and the count tensor, with no host synchronisation."""
+        H, W = disp.shape
+        kw = self._cloud_kwargs(H, W)
+        if colors is None:
+            v = self.__dict__.get("_left_rect")
+            v = v.t if isinstance(v, _HostView) else v
+            if hasattr(v, "is_cuda") and v.is_cuda and v.device == disp.device and \
+                    tuple(v.shape[:2]) == (H, kw['x0'] + W):
+                colors = v
+        return point_cloud_device(disp, colors=colors, stream=stream, sync=sync, **kw)
+
+    @staticmethod
+    def _torch_device_ok() -> bool:
+        try:
+            import torch
+        except ImportError:  # pragma: no cover - torch is part of the image
+            return False
+        return torch.cuda.is_available()
 
     def estimate_depth(self, left_source, right_source, input_scale=None) -> Tuple[np.ndarray, Optional[np.ndarray]]:
         """stereo_core.py:274-293.  Host arrays in, host arrays out; the work runs on the

@@ -32,7 +32,10 @@
 extern "C" {
 #endif
 
-#define DSX_VERSION 106 /* additive since 1.0.6 (layouts unchanged): dsx_confidence, dsx_default_confidence,
+#define DSX_VERSION 106 /* additive since 1.0.6 (layouts unchanged): dsx_cloud, dsx_check_cloud,
+                           dsx_reproject_device, dsx_point_cloud_workspace_bytes, dsx_point_cloud_device
+                           (disparity -> XYZ, ordered point-cloud compaction);
+                           dsx_confidence, dsx_default_confidence,
                            dsx_check_confidence, dsx_set_confidence, dsx_compute_conf_device, dsx_compute_conf_host
                            (matcher confidence map + threshold);
                            dsx_refine, dsx_default_refine, dsx_check_refine,
@@ -517,6 +520,65 @@ int dsx_postprocess_refine_device(const void *d_disp, int32_t H, int32_t W, int6
 int dsx_process_pair_refine_device(dsx_handle *h, const void *dL, const void *dR, int32_t H, int32_t W,
                                    int64_t stride_bytes, const dsx_post_params *pp, void *d_out_disp,
                                    void *d_out_depth, void *hip_stream, const dsx_refine *rf);
+
+/* Point-cloud output: a finished disparity map reprojected to metric XYZ, either organized (one point per
+ * pixel) or compacted to the list of its valid points in row-major pixel order, with colours and pixel
+ * indices.  An addition of this build (as the prefilter, the census costs and the refinement are): parity
+ * with nothing outside this repository is claimed.  Stateless calls on a float32 H x W map d whose column 0
+ * is image column x0 (the crop: num_disp for the maps of dsx_process_pair_device).  All values float32, every
+ * operation correctly rounded, no FMA (host restatement: depthestimation_amd/pointcloud.py, equal bit for
+ * bit, the count and the order included):
+ *   fB  = (float)((double)focal_length * (double)baseline)      the depth map's own constant
+ *   adj = d + doffs;  Z = fB / adj
+ *   valid = adj > eps  and  0 < Z < +inf  and  (not has_max_depth or Z <= max_depth)     (NaN: invalid)
+ *   s = Z / focal_length;  X = ((float)(x + x0) - cx) * s;  Y = ((float)y - cy) * s
+ * Axes as cv2's: x right, y down, z forward.  Points beyond max_depth are dropped, not clamped as the depth
+ * map clamps them; a valid point's Z has the depth map's bits wherever that depth is below max_depth.
+ * Results in the denormal range are outside the contract. */
+typedef struct dsx_cloud {
+    double focal_length; /* pixels, > 0: doubles as in dsx_post_params, so that */
+    double baseline;     /* metres, finite, != 0: fB is the depth map's own     */
+    float cx, cy;      /* principal point in UNCROPPED image coordinates       */
+    float doffs;        /* finite                                               */
+    float eps;          /* finite (StereoCore passes min_disp)                  */
+    float max_depth;    /* > 0 when has_max_depth                               */
+    int32_t has_max_depth; /* 0 | 1                                             */
+    int32_t x0;         /* >= 0: image column of the map's column 0             */
+    int32_t reserved;
+} dsx_cloud;
+
+/* Validate a reprojection (host only, no device): focal_length > 0 and finite, baseline finite and != 0,
+ * cx / cy / doffs / eps finite, has_max_depth 0 | 1 with max_depth > 0 (not NaN) when set, x0 >= 0. */
+int dsx_check_cloud(const dsx_cloud *c);
+
+/* The organized map.  d_disp: float32 H x W, row pitch `in_pitch` elements; d_xyz: contiguous float32
+ * H x W x 3, all three components NaN at invalid pixels.  One launch, asynchronous on hip_stream.
+ * H == 0 or W == 0: nothing to do.  H * W <= 2^31 - 1, x0 + W <= 2^31 - 1. */
+int dsx_reproject_device(const void *d_disp, int32_t H, int32_t W, int64_t in_pitch, const dsx_cloud *c,
+                         void *d_xyz, void *hip_stream);
+
+/* Bytes of d_workspace for dsx_point_cloud_device: one int32 per tile of DSX_CLOUD_TILE consecutive pixels
+ * (0 for an empty or invalid shape). */
+#define DSX_CLOUD_TILE 2048
+int64_t dsx_point_cloud_workspace_bytes(int32_t H, int32_t W);
+
+/* The compact cloud: the valid points of d in row-major pixel order.
+ *   d_points  float32 cap x 3 (X, Y, Z);  d_colors  uint8 cap x 3 RGB, or NULL;  d_index  int32 cap holding
+ *   y * W + x (to gather confidence or anything else per point), or NULL;  d_count  one int32: the number N
+ *   of valid points, always the true count - N > cap tells the caller that only the first cap points were
+ *   written.  Nothing at or past cap is touched in any output.
+ *   d_color  with d_colors: the UNCROPPED uint8 image H x (x0 + W) x channels on the same device, row pitch
+ *   color_pitch_bytes (any alignment), read from column x0 on; channels 3: BGR, swapped to RGB; 1: gray,
+ *   replicated; 0 (or d_colors NULL): no colours, d_color unused.
+ * Three launches on hip_stream - per-tile counts (ballot + popcount), one block's exclusive scan of the tile
+ * counts, and a scatter that recomputes the points, ranks them inside the tile (ballot + mbcnt) and writes them
+ * into the tile's contiguous output range - with no block waiting on another, no atomics, no host
+ * synchronisation.  H == 0 or W == 0 writes count 0 and launches nothing else (d_workspace may be NULL).
+ * Argument errors (NULL or short arguments included) are DSX_EINVAL before any HIP call. */
+int dsx_point_cloud_device(const void *d_disp, int32_t H, int32_t W, int64_t in_pitch, const dsx_cloud *c,
+                           const void *d_color, int64_t color_pitch_bytes, int32_t channels, void *d_points,
+                           void *d_colors, void *d_index, int64_t cap, void *d_count, void *d_workspace,
+                           int64_t workspace_bytes, void *hip_stream);
 
 /* Per-frame rectification on the device, replacing cv2.cvtColor(BGR2GRAY)
  * + cv2.remap(INTER_LINEAR) of rectify.py:183-186 (cached-maps path) and stereo_core.py:155-159:
