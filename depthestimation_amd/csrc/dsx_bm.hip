@@ -108,6 +108,14 @@ constexpr bool kRowstepDivq = DSX_ROWSTEP_DIVQ;          // pair layout, left pa
 #define DSX_ROWSTEP_MERGE 1
 #endif
 constexpr bool kRowstepMerge = DSX_ROWSTEP_MERGE;  // one load and one 16-B store per staged row
+// -DDSX_ROWSTEP_COLGROUP=0 restores the single-column sums of the 9x9 and 3x3 rotated loops (CG in bm2_segment): with
+// it the unaligned-dword copy of bm2<4, SAD, 1, 0> and bm2<1, SAD, 1, 0> keeps, per column c, the sum of columns c,
+// c + 1 and c + 2 over the live rows.  The staged words are 3-byte windows, so one v_sad_u8 adds a whole entering or
+// leaving 3-column term, and a 9-column box is one v_add3_u32 of three group sums (profiles/colgroup_isa.txt).
+#ifndef DSX_ROWSTEP_COLGROUP
+#define DSX_ROWSTEP_COLGROUP 1
+#endif
+constexpr bool kRowstepColgroup = DSX_ROWSTEP_COLGROUP;
 constexpr bool kRowstepAtid = DSX_ROWSTEP_ATID;
 constexpr bool kRowstepKey2 = DSX_ROWSTEP_KEY2;
 // Segment-start forms (the code between kernel entry and a segment's first row step), each behind its own switch
@@ -179,6 +187,13 @@ __device__ __forceinline__ int mad_i24(int a, int b, int c) {
     asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
 }
+// a + b + c in one v_add3_u32.  Written out: from the plain sum of three group sums per pixel hipcc shares partial
+// sums between the pixels of a box phase (35 v_add_u32 + 5 v_add3_u32 in dependent runs instead of 32 independent ops).
+__device__ __forceinline__ uint32_t add3_u32(uint32_t a, uint32_t b, uint32_t c) {
+    uint32_t r;
+    asm("v_add3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
 // c + (|a - b| summed over the 4 bytes << 16): with zero-extended bytes in a and b the absolute
 // difference lands in the high u16 half of a packed pair (v_sad_u8 is the low half's form); both
 // issue in 4.15 cycles (tools/ubench3.hip) against 2 v_pk_* + 2 v_add/sub_u32 for max - min.  The
@@ -231,6 +246,7 @@ template <int R, bool SSD, int NW>
 struct Geo {
     static constexpr int TX = 32;
     static constexpr int NC = TX + 2 * R;     // column sums per lane (even)
+    static constexpr int NG3 = NC - 2;        // 3-column group sums per lane (the forms that keep them: CG in bm2_segment)
     static constexpr int KD = SSD ? 1 : 2;    // disparities per lane
     static constexpr int LDW = 64 * KD;       // disparities per wave
     static constexpr int Dp = NW * LDW;
@@ -409,12 +425,33 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
     // at R = 4, 8 B).
     constexpr bool MRG = kRowstepMerge && RL2 && FAST && SIDE != 3 && SIDE != 2 && !(SIDE == 4 && R >= 7);
     static_assert(!MRG || NJ4 + NC4 <= NT, "merged staging: a lane per staged dword");
+    // CG (the unaligned-dword copy of the rotated 9x9 and 3x3 loops): 3-column group sums.  cs[c], c < NG3, holds
+    // G3[c] = the sums of columns c, c + 1, c + 2 over the live rows, in both halves; the window is 3 x 3 (R = 4) or 1
+    // (R = 1) of them.  A staged searched entry j is the 3-byte window {p(pos(j)), p(pos(j) + 1), p(pos(j) + 2), 0}
+    // and a staged reference column c is {r(c), r(c + 1), r(c + 2), 0}: pos(c + i, d) = pos(c, d) + i, so one
+    // v_sad_u8 of the two adds the three columns' terms of one row and disparity.  Same integers in another order:
+    // a half of G3 is at most 3 * 9 * 255 = 6,885 and a half of a box sum 20,655, so no half carries.
+    //   staging: a lane's four windows take six source bytes, its own dword and the next one in x.  For a searched
+    //     lane that is lane tid - 1's dword (the entries run down with x); the reference lanes are ordered down as
+    //     well, so one DPP move (wave_shr:1) per staged row serves both roles, and the four v_perm_b32 select from
+    //     the two dwords.  The bytes no lane holds - past lane 0's and the first reference lane's dword - only
+    //     reach entries 0, 1 and columns >= NG3, which nothing reads.
+    //   row step: NG3 groups instead of NC columns, read at entries d0 + 2 .. d0 + NC.
+    //   segment start: the init forms the single-column sums as before; G3 is summed from them once, in place.
+    //   box phase: v[k] = G3[k] + G3[k + 3] + G3[k + 6] (R = 4), G3[k] (R = 1): no running sum.
+    // The clamped copy keeps the single-column form; a segment is wholly one or the other.
+    constexpr bool CG = kRowstepColgroup && MRG && SIDE == 0 && NW == 1 && (R == 4 || R == 1) && kRowstepKey2 &&
+                        !kRowstepPairtail && kRowstepOverlap && kRowstepAhead && !kRowstepSref;
+    constexpr int NCU = CG ? G::NG3 : NC;  // columns (groups) of the rotated loop's column update
     const bool m_s = tid < NJ4;
-    const int m_r = min(tid - NJ4, NC4 - 1);  // reference dword of a non-search lane
+    const int m_r = CG ? max(NC4 - 1 - (tid - NJ4), 0) : min(tid - NJ4, NC4 - 1);  // reference dword of a non-search lane
     const uint8_t *m_base = m_s ? a.src + fin + ofs_s : a.ref + fin + (uint32_t)(x0 - R + 4 * m_r);
     const bool m_dn = m_s && side != 1;  // bytes 3, 2, 1, 0 -> words 0 .. 3
-    const uint32_t m_sel0 = m_dn ? 0x0C0C0C03u : 0x0C0C0C00u, m_sel1 = m_dn ? 0x0C0C0C02u : 0x0C0C0C01u,
-                   m_sel2 = m_dn ? 0x0C0C0C01u : 0x0C0C0C02u, m_sel3 = m_dn ? 0x0C0C0C00u : 0x0C0C0C03u;
+    // CG: bytes 0 .. 3 are the lane's dword, 4 .. 7 the next one in x
+    const uint32_t m_sel0 = CG ? (m_dn ? 0x0C050403u : 0x0C020100u) : (m_dn ? 0x0C0C0C03u : 0x0C0C0C00u),
+                   m_sel1 = CG ? (m_dn ? 0x0C040302u : 0x0C030201u) : (m_dn ? 0x0C0C0C02u : 0x0C0C0C01u),
+                   m_sel2 = CG ? (m_dn ? 0x0C030201u : 0x0C040302u) : (m_dn ? 0x0C0C0C01u : 0x0C0C0C02u),
+                   m_sel3 = CG ? (m_dn ? 0x0C020100u : 0x0C050403u) : (m_dn ? 0x0C0C0C00u : 0x0C0C0C03u);
     const uint32_t m_lane = m_s ? (uint32_t)(16 * tid) : (uint32_t)(G::SROW + 16 * m_r);  // byte offset in a slot
     auto ldm = [&](int r, uint32_t &w) __attribute__((always_inline)) {
         const int yy = clampi2(r, 0, H - 1);
@@ -423,9 +460,11 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
         w = *reinterpret_cast<const uint32_t *>(m_base + ro);
     };
     auto stm = [&](uint8_t *sp, uint32_t w) __attribute__((always_inline)) {
+        // CG: lane tid - 1's dword (lane 0: zero); the lanes that store and their sources are all active
+        const uint32_t nb = CG ? (uint32_t)__builtin_amdgcn_mov_dpp((int)w, 0x138, 0xF, 0xF, true) : 0u;
         if (tid < NJ4 + NC4)
-            *reinterpret_cast<uint4 *>(sp) = make_uint4(__builtin_amdgcn_perm(0u, w, m_sel0), __builtin_amdgcn_perm(0u, w, m_sel1),
-                                                        __builtin_amdgcn_perm(0u, w, m_sel2), __builtin_amdgcn_perm(0u, w, m_sel3));
+            *reinterpret_cast<uint4 *>(sp) = make_uint4(__builtin_amdgcn_perm(nb, w, m_sel0), __builtin_amdgcn_perm(nb, w, m_sel1),
+                                                        __builtin_amdgcn_perm(nb, w, m_sel2), __builtin_amdgcn_perm(nb, w, m_sel3));
     };
     // SR0 (the builds that batch their init rows, IBT below, and stage merged rows): step yb's prefetch - rows
     // yb + 1 + R and yb - R, the one an init row again - issued once the init batch is in LDS, in front of the init SAD
@@ -830,6 +869,10 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
             if constexpr (ABS) cs[c] = ae[c];
             else cs[c] = as2(ae[c] | (ao[c] << 16));  // <= 255 (2R+1) < 2^16
         }
+        if constexpr (CG) {  // the group sums, in place and ascending (cs[NG3], cs[NG3 + 1] are dead behind this)
+#pragma unroll
+            for (int c = 0; c < G::NG3; ++c) cs[c] = as2(as1(cs[c]) + as1(cs[c + 1]) + as1(cs[c + 2]));
+        }
         }
 
     } else {
@@ -934,7 +977,8 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
     constexpr bool STL = kRowstepStorelate && OVL;
     int e_fx = 0;
     float e_pf = 0.0f;
-    constexpr int CQ = 4, NQ = (NC + CQ - 1) / CQ;
+    static_assert(!CG || (CUQ && OVL && AHD), "group sums: the rotated loop with its reads ahead");
+    constexpr int CQ = 4, NQ = (NCU + CQ - 1) / CQ;
     // SREF (the unaligned-dword copy of these loops): the reference row is wave-uniform, so the column update takes
     // it from SGPRs - v_sad_u8 / v_sad_hi_u8 are VOP3 and read the reference byte as their one scalar operand -
     // instead of 2 * NC4 broadcast ds_read_b128 per step.  A row is bytes [x0 - R, x0 - R + 4 NC4) of the reference
@@ -1195,7 +1239,7 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
                 so[t][0] = c0 == 0 ? *reinterpret_cast<const uint32_t *>(bo + NC * 4) : nxo;
 #pragma unroll
                 for (int c = 1; c < CQ; c += 2) {
-                    if (c0 + c < NC) {
+                    if (c0 + c < NCU) {
                         const u32x2 pn = lds_read_b64(bn + (NC - 1 - c0 - c) * 4);
                         const u32x2 po = lds_read_b64(bo + (NC - 1 - c0 - c) * 4);
                         sn[t][c + 1] = pn.x; sn[t][c] = pn.y; nxn = pn.x;
@@ -1218,7 +1262,7 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
                 }
 #pragma unroll
                 for (int c = 0; c < CQ; ++c) {
-                    if (c0 + c < NC) {
+                    if (c0 + c < NCU) {
                         const uint32_t bn = SREF ? sbyte(wn, c) : rn[t][c], bo = SREF ? sbyte(wo, c) : ro[t][c];
                         const uint32_t en = sad_hi_u8(bn, sn[t][c], __builtin_amdgcn_sad_u8(bn, sn[t][c + 1], as1(cs[c0 + c])));
                         const uint32_t lo = sad_hi_u8(bo, so[t][c], __builtin_amdgcn_sad_u8(bo, so[t][c + 1], 0u));
@@ -1331,10 +1375,12 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
             };
             acc_t acc = cs[0];
             if constexpr (FSS) acc = 8388608.0f + cs[0];  // + 2^23 (see FSS)
+            if constexpr (!CG) {
 #pragma unroll
             for (int c = 1; c <= 2 * R; ++c) {
                 if constexpr (SSD) acc += cs[c];
                 else acc = as2(as1(acc) + as1(cs[c]));
+            }
             }
             if constexpr (side == 3) {
                 // Right-view winners along the tile's diagonals: C_R(xr, d) = C(xr + m + d, d), so
@@ -1456,8 +1502,12 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
                     uint32_t v[8];
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
-                        if (k0 + j > 0) acc = add_sub2(acc, cs[k0 + j + 2 * R], cs[k0 + j - 1]);
-                        v[j] = as1(acc);
+                        if constexpr (CG) {  // three group sums (R = 4) or one (R = 1): independent, no running sum
+                            v[j] = R == 4 ? add3_u32(as1(cs[k0 + j]), as1(cs[k0 + j + 3]), as1(cs[k0 + j + 6])) : as1(cs[k0 + j]);
+                        } else {
+                            if (k0 + j > 0) acc = add_sub2(acc, cs[k0 + j + 2 * R], cs[k0 + j - 1]);
+                            v[j] = as1(acc);
+                        }
                     }
                     lds_store8_addtid<k0 * PITCH, PITCH>(mb, v);
                 };

@@ -13,6 +13,7 @@ loop of an instantiation (the unaligned-dword copy and the clamped-byte copy of 
     cycles per wave-instruction for conflict-free accesses; a store's cycles are those of moving its
     address and data dwords to the LDS).  Static counts over every block of the loop, the branches a
     benchmark step does not take included (odd-D overwrite, uniqueness re-reads, edge overwrites);
+  * the SAD, add / sub, add3, byte-permute and DPP-move counts (column update, box phase, staging);
   * the kernel's VGPRs, scratch bytes and LDS bytes per block (Geo in dsx_bm.hip, restated here);
   * a segment-start table (segstart_report below): LDS drains of the init SAD loop, loads, vmcnt waits and global
     round trips of the init rows, memory waits in front of the segment loop.
@@ -213,6 +214,10 @@ def report(asm, name, out):
         out(f"    LDS: {txt}")
         out(f"    LDS-path cycles per wave (static): {cyc}; s_nop {cnt('s_nop')}, v_readfirstlane {cnt('v_readfirstlane')}, "
             f"v_lshl_add_u64 {cnt('v_lshl_add_u64')}")
+        # the column update and the box phase by opcode (the pair layout's byte SADs, their subtractions, the box sums)
+        out(f"    sums: v_sad_u8 {cnt('v_sad_u8')}, v_sad_hi_u8 {cnt('v_sad_hi_u8')}, v_sub_u32 {cnt('v_sub_u32')}, "
+            f"v_add_u32 {cnt('v_add_u32')}, v_add3_u32 {cnt('v_add3_u32')}, v_perm_b32 {cnt('v_perm_b32')}, "
+            f"v_mov_b32_dpp {cnt('v_mov_b32_dpp')}")
         # The compiler lays the blocks of a step out of program order (the column update and the
         # box phase sit behind the stores in the listing), so positions are taken from the control
         # flow: op k leads to op k + 1 (unless it is s_branch) and to its branch target.  The step
