@@ -16,6 +16,11 @@ per device, results yielded in frame order).
 
 ``configure_sgbm(confidence_threshold=t)`` is honoured by every form; the generator yields depth maps only
 and returns no confidence map.
+
+``configure_sgbm(temporal='recursive')`` (the temporal disparity filter, temporal.py) is honoured by the
+single-device forms - the plain loop and ``devices=[d]`` - where consecutive frames meet in one place.
+``devices`` with more than one entry and ``world_size > 1`` spread consecutive frames over devices or
+processes: ``estimate_depth()`` raises ValueError for them.
 """
 from __future__ import annotations
 
@@ -84,6 +89,14 @@ class StereoDepthEstimatorVideo:
         """Yields depth_m per frame (this rank's frames when sharded)."""
         if self.left_source is None or self.right_source is None:
             raise ValueError("Both left_source and right_source must be provided for video depth estimation.")
+        if self.core.sgbm_params.get('temporal', 'none') != 'none':
+            # the filter's state follows one sequence on one device: consecutive frames must meet there
+            if self.devices and len(self.devices) > 1:
+                raise ValueError("'temporal' needs consecutive frames on one device: it cannot run with "
+                                 f"devices={self.devices} (use one device, or 'temporal': 'none')")
+            if not self.devices and self.world_size > 1:
+                raise ValueError("'temporal' needs consecutive frames in one process: it cannot run with "
+                                 f"world_size={self.world_size} (use one rank, or 'temporal': 'none')")
         self.core.configure_sgbm(**self.core.get_sgbm_params())
         if self.visualize_live:
             warnings.warn("visualize_live: no GUI in this build; frames are only yielded", RuntimeWarning)

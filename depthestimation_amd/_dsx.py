@@ -47,6 +47,9 @@ EXPORTS = (
     "dsx_default_confidence", "dsx_check_confidence", "dsx_set_confidence", "dsx_compute_conf_device",
     "dsx_compute_conf_host",
     "dsx_check_cloud", "dsx_reproject_device", "dsx_point_cloud_workspace_bytes", "dsx_point_cloud_device",
+    "dsx_default_temporal", "dsx_check_temporal", "dsx_temporal_gains", "dsx_tfilter_create",
+    "dsx_tfilter_set_params", "dsx_tfilter_reset", "dsx_tfilter_bytes", "dsx_tfilter_destroy",
+    "dsx_tfilter_run_device",
 )
 
 
@@ -138,6 +141,23 @@ class DsxCloud(ctypes.Structure):
     ]
 
 
+TEMPORAL = {"none": 0, "recursive": 1}  # DSX_TEMPORAL_* (include/dsx.h)
+TEMPORAL_TILE = (256, 8)  # (DSX_TEMPORAL_TILE_W, DSX_TEMPORAL_TILE_H): pixels per block of the temporal filter
+
+
+class DsxTemporalParams(ctypes.Structure):
+    """dsx_temporal_params (include/dsx.h): the temporal disparity filter."""
+    _fields_ = [
+        ("type", ctypes.c_int32),
+        ("max_age", ctypes.c_int32),
+        ("max_diff", ctypes.c_float),
+        ("motion_radius", ctypes.c_int32),
+        ("motion_threshold", ctypes.c_int32),
+        ("hold", ctypes.c_int32),
+        ("reserved", ctypes.c_int32 * 6),
+    ]
+
+
 POST_MODE = {"fast": 1, "full": 2}  # DSX_POST_* (include/dsx.h)
 FILL_METHOD = {"inpaint": 0, "nearest": 1}  # DSX_FILL_* (fill_holes' method names, postprocess.py:72-118)
 NEAREST_PATH = {"auto": 0, "fused": 1, "stepwise": 2}  # DSX_NEAREST_*
@@ -189,7 +209,19 @@ def _bind(lib):
     CF = ctypes.POINTER(DsxConfidence)
     PP = ctypes.POINTER(DsxPostParams)
     CL = ctypes.POINTER(DsxCloud)
+    TP = ctypes.POINTER(DsxTemporalParams)
+    dbl = ctypes.c_double
     sig = {
+        "dsx_default_temporal": (None, [TP]),
+        "dsx_check_temporal": (ctypes.c_int, [TP]),
+        "dsx_temporal_gains": (ctypes.c_int, [i32, ctypes.POINTER(ctypes.c_float)]),
+        "dsx_tfilter_create": (ctypes.c_int, [ctypes.c_int, TP, ctypes.POINTER(vp)]),
+        "dsx_tfilter_set_params": (ctypes.c_int, [vp, TP]),
+        "dsx_tfilter_reset": (ctypes.c_int, [vp]),
+        "dsx_tfilter_bytes": (ctypes.c_int, [vp, ctypes.POINTER(i64)]),
+        "dsx_tfilter_destroy": (ctypes.c_int, [vp]),
+        "dsx_tfilter_run_device": (ctypes.c_int, [vp, vp, i32, i32, i64, vp, i64, vp, vp, dbl, dbl, dbl, dbl, dbl, i32,
+                                                   vp]),
         "dsx_check_cloud": (ctypes.c_int, [CL]),
         "dsx_reproject_device": (ctypes.c_int, [vp, i32, i32, i64, CL, vp, vp]),
         "dsx_point_cloud_workspace_bytes": (i64, [i32, i32]),
@@ -410,6 +442,30 @@ def make_cloud(focal_length, baseline, cx, cy, doffs=0.0, eps=1e-6, max_depth=No
     c.x0 = int(x0)
     check(lib().dsx_check_cloud(ctypes.byref(c)), "dsx_check_cloud")
     return c
+
+
+def make_temporal(temporal="recursive", max_age=4, max_diff=1.0, motion_radius=1, motion_threshold=6,
+                  hold=2) -> DsxTemporalParams:
+    """dsx_temporal_params from the filter's keywords; ValueError for an unknown name or a value
+    dsx_check_temporal refuses."""
+    t = DsxTemporalParams()
+    lib().dsx_default_temporal(ctypes.byref(t))
+    if temporal is None:
+        temporal = "none"
+    if temporal not in TEMPORAL:
+        raise ValueError(f"temporal must be one of {list(TEMPORAL)}, got {temporal!r}")
+    t.type = TEMPORAL[temporal]
+    for name, v in (("max_age", max_age), ("motion_radius", motion_radius), ("motion_threshold", motion_threshold),
+                    ("hold", hold)):
+        if isinstance(v, bool) or int(v) != v or abs(int(v)) > 1 << 30:
+            raise ValueError(f"temporal {name} must be an integer")
+        setattr(t, name, int(v))
+    try:
+        t.max_diff = float(max_diff)
+    except (TypeError, ValueError, OverflowError) as e:
+        raise ValueError("temporal max_diff must be a finite number > 0") from e
+    check(lib().dsx_check_temporal(ctypes.byref(t)), "dsx_check_temporal")
+    return t
 
 
 def check_prefilter(p, f: DsxPrefilter) -> None:

@@ -925,3 +925,92 @@ def fill_holes_device(disp, radius=5, out=None, stream=None, workspace=None, spi
     _dsx.check(rc, "dsx_fill_holes_ex_device")
     _keep_until_done(ws, stream)
     return out
+
+
+class TemporalFilterDevice:
+    """The temporal disparity filter on one HIP device (dsx_tfilter, include/dsx.h; host restatement
+    depthestimation_amd/temporal.py ``TemporalFilter``, equal bit for bit on every frame): a motion-gated
+    recursive average of the finished disparity maps of a video with a temporal hole filler.  The object owns
+    the state (filtered disparity, age, hold count, previous guide); a frame of another shape reallocates and
+    resets it.  Frames are filtered in the order of the ``run`` calls whatever their streams: the library
+    orders a call on another stream behind the previous call's kernel (an event, no host wait), so one object
+    serves a pipeline with several frames in flight.  One caller at a time."""
+
+    def __init__(self, device=0, max_age=4, max_diff=1.0, motion_radius=1, motion_threshold=6, hold=2):
+        self.device = int(device)
+        self._params = _dsx.make_temporal("recursive", max_age, max_diff, motion_radius, motion_threshold, hold)
+        self._f = None
+
+    def _filter(self):
+        if self._f is None:
+            if _dsx.device_count() == 0:
+                raise RuntimeError("TemporalFilterDevice: no HIP device visible (the engine has no CPU fallback)")
+            f = ctypes.c_void_p()
+            _dsx.check(_dsx.lib().dsx_tfilter_create(self.device, ctypes.byref(self._params), ctypes.byref(f)),
+                       "dsx_tfilter_create")
+            self._f = f
+        return self._f
+
+    def set_params(self, max_age=4, max_diff=1.0, motion_radius=1, motion_threshold=6, hold=2):
+        """Replace the parameters (dsx_tfilter_set_params); the state is reset."""
+        t = _dsx.make_temporal("recursive", max_age, max_diff, motion_radius, motion_threshold, hold)
+        if self._f is not None:
+            _dsx.check(_dsx.lib().dsx_tfilter_set_params(self._f, ctypes.byref(t)), "dsx_tfilter_set_params")
+        self._params = t
+
+    def reset(self):
+        """The next frame has no previous frame."""
+        if self._f is not None:
+            _dsx.check(_dsx.lib().dsx_tfilter_reset(self._f), "dsx_tfilter_reset")
+
+    def state_bytes(self) -> int:
+        b = ctypes.c_int64(0)
+        _dsx.check(_dsx.lib().dsx_tfilter_bytes(self._filter(), ctypes.byref(b)), "dsx_tfilter_bytes")
+        return b.value
+
+    def run(self, disp, guide, out=None, focal_length=None, baseline=None, doffs=0.0, eps=1e-6, max_depth=None,
+            out_depth=None, stream=None):
+        """One frame, asynchronous on ``stream`` (dsx_tfilter_run_device).  ``disp``: float32 H x W HIP tensor,
+        ``guide``: uint8 H x W HIP tensor over the same pixels (both unit column stride, any row stride or
+        offset: the pitched view ``left[:, num_disp:]`` is fine).  ``out``: a contiguous float32 H x W tensor,
+        which may be ``disp`` itself when that is contiguous; None allocates one.  With ``focal_length`` and
+        ``baseline`` the same launch writes the depth of the filtered map (``StereoCore.disparity_to_depth``,
+        bit for bit).  Returns (out, depth or None)."""
+        import torch
+
+        if not hasattr(disp, "dtype") or disp.dtype != torch.float32 or disp.dim() != 2 or not disp.is_cuda or \
+                (disp.shape[1] > 1 and disp.stride(1) != 1):
+            raise ValueError("disp must be a float32 H x W device tensor with unit column stride")
+        if not hasattr(guide, "dtype") or guide.dtype != torch.uint8 or guide.shape != disp.shape or \
+                guide.device != disp.device or (guide.shape[1] > 1 and guide.stride(1) != 1):
+            raise ValueError("guide must be a uint8 tensor of disp's shape on its device with unit column stride")
+        _check_inputs_on(self.device, disp, guide)
+        H, W = disp.shape
+        if out is None:
+            out = torch.empty((H, W), dtype=torch.float32, device=disp.device)
+        _check_out(out, (H, W), "torch.float32", self.device, "out")
+        want_depth = focal_length is not None and baseline is not None
+        if want_depth and out_depth is None:
+            out_depth = torch.empty((H, W), dtype=torch.float32, device=disp.device)
+        if want_depth:
+            _check_out(out_depth, (H, W), "torch.float32", self.device, "out_depth")
+        if H == 0 or W == 0:
+            return out, (out_depth if want_depth else None)
+        rc = _dsx.lib().dsx_tfilter_run_device(
+            self._filter(), disp.data_ptr(), H, W, max(disp.stride(0), W) if H > 1 else W, guide.data_ptr(),
+            max(guide.stride(0), W) if H > 1 else W, _ptr(out), _ptr(out_depth) if want_depth else None,
+            float(focal_length or 0.0), float(baseline or 0.0), float(doffs or 0.0), float(eps),
+            float(max_depth or 0.0), int(max_depth is not None), _stream_ptr(stream))
+        _dsx.check(rc, "dsx_tfilter_run_device")
+        return out, (out_depth if want_depth else None)
+
+    def close(self):
+        if self._f is not None:
+            _dsx.lib().dsx_tfilter_destroy(self._f)
+            self._f = None
+
+    def __del__(self):  # pragma: no cover - GC timing
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -344,7 +344,12 @@ class DepthPipeline:
     frame's stream, equal bit for bit to pushing ``resize_area`` of the frames.
 
     The core's 'confidence_threshold' is honoured; the pipeline returns no confidence map (with
-    'confidence': True each slot's core keeps its last frame's map, which no result carries)."""
+    'confidence': True each slot's core keeps its last frame's map, which no result carries).
+
+    'temporal': 'recursive' is honoured: the per-slot copies of the core share its one temporal filter, which
+    every frame calls in push order on the frame's own stream; the library orders each call behind the previous
+    frame's filter launch (an event between the streams, no host wait), so the frames are filtered in order
+    while frame i + 1's matcher still overlaps frame i.  Frames must be pushed in sequence order."""
 
     def __init__(self, core, device: int, depth: int = 3, streams: int = 2, input_scale=None):
         import copy

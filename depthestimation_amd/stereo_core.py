@@ -64,6 +64,17 @@ Keys added to ``sgbm_params`` (accepted by ``configure_sgbm`` like the reference
                                        pixel coordinates, scaled by downscale_factor like 'focal_length'; used
                                        by ``point_cloud`` (pointcloud.py: disparity -> XYZ + RGB).  None: with
                                        a full calibration the rectification's own P1, else the image centre)
+  'temporal': 'none' | 'recursive'    ('none', the default.  'recursive': the temporal disparity filter of temporal.py
+                                       behind the mode's tail (fast and full mode alike) - a motion-gated
+                                       recursive average of the finished maps of consecutive frames that also
+                                       holds a static pixel's last value over short holes, guided by the raw
+                                       left rectified image.  It removes the frame-to-frame flicker of block
+                                       matching on video; the state lives in this core (``reset_temporal()``
+                                       forgets it, as any ``configure_sgbm`` and any change of the frame's
+                                       shape do), so frames must arrive in order.  'temporal_max_age' 1..64 (4),
+                                       'temporal_max_diff' > 0 px (1.0), 'temporal_motion_radius' 0..2 (1),
+                                       'temporal_motion_threshold' 0..255 grey levels per tap (6),
+                                       'temporal_hold' 0..255 frames (2))
 Keys of the reference that have no block-matching meaning are kept, validated and reported
 but do not change the result: 'prefilter_cap' unless 'cost' is 'bt' or a prefilter is set, 'speckle_window_size' /
 'speckle_range' unless 'sgbm_post' is set, and 'sgbm_mode' / P1 / P2 while 'aggregation' is 'none'
@@ -79,10 +90,11 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 
 from .input import resize_area, resize_area_device
-from .matcher import (HipBlockMatcher, default_workspace, fill_holes_status, postprocess_fast_device,
+from .matcher import (HipBlockMatcher, TemporalFilterDevice, default_workspace, fill_holes_status, postprocess_fast_device,
                       point_cloud_device, postprocess_full_device, rectify_device)
 from .pointcloud import point_cloud as host_point_cloud
 from .postprocess import median_blur3, postprocess_disparity
+from .temporal import TemporalFilter, check_temporal
 from .rectify import RectificationCache, rectified_principal_point, rectify_images, to_grayscale_bgr
 
 _SGBM_MODES = ("sgbm", "hh", "sgbm_3way", "hh4")
@@ -105,6 +117,41 @@ class _HostView:
 
     def __init__(self, t):
         self.t = t
+
+
+class _TemporalState:
+    """The temporal filter of one StereoCore: the parameters, the host restatement (the host path) and the
+    device object (the device routes), each created on first use.  Shallow copies of a core share it, so the
+    per-slot copies of a ``multigpu.DepthPipeline`` filter one sequence."""
+
+    def __init__(self, **kw):
+        self.kw = kw
+        self.host = None
+        self.dev = None
+
+    def host_filter(self) -> TemporalFilter:
+        if self.host is None:
+            self.host = TemporalFilter(**self.kw)
+        return self.host
+
+    def device_filter(self, device: int) -> TemporalFilterDevice:
+        if self.dev is not None and self.dev.device != device:
+            self.dev.close()
+            self.dev = None
+        if self.dev is None:
+            self.dev = TemporalFilterDevice(device=device, **self.kw)
+        return self.dev
+
+    def reset(self) -> None:
+        if self.host is not None:
+            self.host.reset()
+        if self.dev is not None:
+            self.dev.reset()
+
+    def close(self) -> None:
+        if self.dev is not None:
+            self.dev.close()
+        self.host = self.dev = None
 
 
 class StereoCore:
@@ -181,7 +228,14 @@ class StereoCore:
             'confidence': False,
             'confidence_threshold': 0,
             'principal_point': None,
+            'temporal': 'none',
+            'temporal_max_age': 4,
+            'temporal_max_diff': 1.0,
+            'temporal_motion_radius': 1,
+            'temporal_motion_threshold': 6,
+            'temporal_hold': 2,
         }
+        self._temporal = None
         self._pp_cache = None  # (calibration key, (cx, cy) of the left rectified image)
         self.confidence_map = None
         self._build_sgbm()
@@ -212,6 +266,24 @@ class StereoCore:
             raise ValueError("Invalid parameter value for 'confidence_threshold': expected an integer in [0, 255]")
         if p.get('principal_point') is not None and not _valid_principal_point(p['principal_point']):
             raise ValueError("Invalid parameter value for 'principal_point': expected None or two finite numbers")
+        if p.get('temporal', 'none') not in ('none', 'recursive'):
+            raise ValueError("Invalid parameter value for 'temporal': expected 'none' or 'recursive'")
+        tkw = self._temporal_kwargs()
+        for key, (lo, hi) in (('max_age', (1, 64)), ('motion_radius', (0, 2)), ('motion_threshold', (0, 255)),
+                              ('hold', (0, 255))):
+            try:
+                check_temporal(**{key: tkw[key]})
+            except ValueError:
+                raise ValueError(f"Invalid parameter value for 'temporal_{key}': expected an integer in "
+                                 f"[{lo}, {hi}]") from None
+        try:
+            check_temporal(max_diff=tkw['max_diff'])
+        except ValueError:
+            raise ValueError("Invalid parameter value for 'temporal_max_diff': expected a finite number > 0") from None
+        # any (re)configuration forgets the temporal state; the filter objects are built on first use
+        if getattr(self, '_temporal', None) is not None:
+            self._temporal.close()
+        self._temporal = _TemporalState(**tkw) if p.get('temporal', 'none') == 'recursive' else None
         self.P1 = 8 * p['block_size'] ** 2
         self.P2 = 32 * p['block_size'] ** 2
         self.mode = p.get('sgbm_mode', 'sgbm_3way') if p.get('sgbm_mode') in _SGBM_MODES else 'sgbm_3way'
@@ -265,6 +337,18 @@ class StereoCore:
         return dict(refine=p.get('refine', 'none'), refine_radius=int(p.get('refine_radius', 5)),
                     refine_sigma=int(p.get('refine_sigma', 8)), refine_fill=bool(p.get('refine_fill', True)))
 
+    def _temporal_kwargs(self) -> dict:
+        """The 'temporal_*' keys as the keywords of TemporalFilter / TemporalFilterDevice."""
+        p = self.sgbm_params
+        return dict(max_age=p.get('temporal_max_age', 4), max_diff=p.get('temporal_max_diff', 1.0),
+                    motion_radius=p.get('temporal_motion_radius', 1),
+                    motion_threshold=p.get('temporal_motion_threshold', 6), hold=p.get('temporal_hold', 2))
+
+    def reset_temporal(self) -> None:
+        """Forget the temporal filter's state: the next frame is filtered as a first frame (a scene cut)."""
+        if self._temporal is not None:
+            self._temporal.reset()
+
     def get_sgbm_params(self) -> Dict[str, int]:
         return self.sgbm_params.copy()
 
@@ -297,6 +381,7 @@ class StereoCore:
             disparity_px = self.compute_disparity(left_img, right_img)
             self.confidence_map = None
         disparity_px = disparity_px[:, self.sgbm_params['num_disp']:]
+        guide = np.asarray(left_img)[:, self.sgbm_params['num_disp']:] if self._temporal is not None else None
         refine = self._refine_kwargs()
         if refine['refine'] != 'none' and not self.fast_mode:
             left_img = np.asarray(left_img)[:, self.sgbm_params['num_disp']:]  # the guide: the map's own pixels
@@ -314,6 +399,8 @@ class StereoCore:
                 apply_hole_filling=self.sgbm_params.get('hole_filling', False),
                 **refine,
             )
+        if self._temporal is not None:  # behind the mode's tail, guided by the raw left image
+            disparity_px = self._temporal.host_filter()(np.ascontiguousarray(disparity_px, np.float32), guide)
         f_pixels = self.sgbm_params.get('focal_length', None)
         baseline_m = self.sgbm_params.get('baseline', None)
         doffs = self.sgbm_params.get('doffs', 0.0)
@@ -399,6 +486,21 @@ class StereoCore:
         timed = fill and method == 'inpaint'  # only Telea's persistent launch can time out
         want_conf = bool(p.get('confidence', False)) and 'compute_disparity_device' not in self.__dict__
         self.confidence_map = None
+        if self._temporal is not None:
+            # the chain runs without depth scalars and the filter's launch writes the depth of the filtered map
+            # (no depth map is computed twice); the map is filtered in place
+            d, _ = self._chain_device(left, right, stream, want_conf, method, timed, None, None)
+            if d.shape[1] == 0:
+                return d, (d.clone() if f is not None and B is not None else None)
+            filt = self._temporal.device_filter(left.get_device())
+            return filt.run(d, left[:, p['num_disp']:], out=d, focal_length=f, baseline=B, doffs=doffs, eps=eps,
+                            max_depth=max_depth, stream=stream)
+        return self._chain_device(left, right, stream, want_conf, method, timed, f, B)
+
+    def _chain_device(self, left, right, stream, want_conf, method, timed, f, B):
+        """The per-frame chain of ``process_pair_device`` up to the mode's tail (depth when ``f`` and ``B``)."""
+        p = self.sgbm_params
+        doffs, eps, max_depth = p.get('doffs', 0.0), p.get('min_disp', 5.0), p.get('max_depth')
         if not want_conf and 'compute_disparity_device' not in self.__dict__ and self.sgbm is not None and \
                 getattr(self.sgbm, 'process_pair_device', None) is not None and \
                 getattr(self.sgbm, 'params', {}).get('float_mode', 'fixed') == 'fixed':

@@ -32,7 +32,11 @@
 extern "C" {
 #endif
 
-#define DSX_VERSION 106 /* additive since 1.0.6 (layouts unchanged): dsx_cloud, dsx_check_cloud,
+#define DSX_VERSION 106 /* additive since 1.0.6 (layouts unchanged): dsx_temporal_params, dsx_default_temporal,
+                           dsx_check_temporal, dsx_temporal_gains, dsx_tfilter_create, dsx_tfilter_set_params,
+                           dsx_tfilter_reset, dsx_tfilter_destroy, dsx_tfilter_bytes, dsx_tfilter_run_device
+                           (temporal disparity filter for video: motion-gated recursive average);
+                           dsx_cloud, dsx_check_cloud,
                            dsx_reproject_device, dsx_point_cloud_workspace_bytes, dsx_point_cloud_device
                            (disparity -> XYZ, ordered point-cloud compaction);
                            dsx_confidence, dsx_default_confidence,
@@ -579,6 +583,90 @@ int dsx_point_cloud_device(const void *d_disp, int32_t H, int32_t W, int64_t in_
                            const void *d_color, int64_t color_pitch_bytes, int32_t channels, void *d_points,
                            void *d_colors, void *d_index, int64_t cap, void *d_count, void *d_workspace,
                            int64_t workspace_bytes, void *hip_stream);
+
+/* Temporal disparity filter for video: a motion-gated recursive average with a temporal hole filler.  An
+ * addition of this build (as the prefilter, the census costs, the refinement and the point cloud are): parity
+ * with nothing outside this repository is claimed.  The one stage here that carries STATE from frame to frame;
+ * the state lives in an opaque filter object (dsx_tfilter), not in a matcher handle.
+ * Inputs per frame: d, the finished float32 H x W disparity map (what dsx_process_pair_device or the
+ * post-processing chain returns; row pitch in elements, any alignment), and G, the uint8 guide over the same
+ * pixels (the left rectified image from column num_disp on - the raw image, also when a prefilter is set; row
+ * stride in bytes, any alignment).
+ * State per pixel: S float32 filtered disparity; n uint8 age (0: no state); h uint8 count of consecutive held
+ * frames; P the previous frame's guide.
+ * Gains: A[n] = (float)(1.0 / (n + 1)), n = 1..max_age, in doubles on the host (dsx_temporal_gains; the device
+ * never computes them).
+ * Rule, with r = motion_radius, cx / cy the replicate clamp, all disparity arithmetic float32, every operation
+ * correctly rounded, no FMA:
+ *   v      = 0 < d < +inf                      (NaN, +-0, negatives and +inf are invalid: the refinement's rule)
+ *   M      = sum over |i|, |j| <= r of |G(cx(x+i), cy(y+j)) - P(cx(x+i), cy(y+j))|       (<= 25 * 255)
+ *   static = there is a previous frame  and  M <= motion_threshold * (2r + 1)^2
+ *   v and static and n > 0 and |d - S| <= max_diff:
+ *            S' = S + (d - S) * A[n];  n' = min(n + 1, max_age);  h' = 0;  out = S'
+ *   else v:  S' = d;  n' = 1;  h' = 0;  out = d (the input bits)
+ *   else static and n > 0 and h < hold:
+ *            out = S;  S and n kept;  h' = h + 1                               (the temporal hole filler)
+ *   else:    out = d (the input bits unchanged);  S' = 0;  n' = 0;  h' = 0
+ *   then P <- G.
+ * The first frame, the first frame after a reset and the first frame after a shape change have no previous
+ * frame: out = d and the state is initialised from d.  Host restatement: depthestimation_amd/temporal.py,
+ * equal bit for bit on every frame. */
+#define DSX_TEMPORAL_NONE 0
+#define DSX_TEMPORAL_RECURSIVE 1
+typedef struct dsx_temporal_params {
+    int32_t type;             /* DSX_TEMPORAL_*                                                    */
+    int32_t max_age;          /* 1..64 (4): the average covers at most max_age + 1 frames           */
+    float max_diff;           /* finite, > 0, pixels (1.0): a larger step restarts the average      */
+    int32_t motion_radius;    /* 0..2 (1)                                                          */
+    int32_t motion_threshold; /* 0..255 grey levels per tap (6)                                    */
+    int32_t hold;             /* 0..255 frames (2): how long a static pixel's hole shows its state  */
+    int32_t reserved[6];
+} dsx_temporal_params;
+
+/* recursive, max_age 4, max_diff 1.0, radius 1, threshold 6, hold 2 */
+void dsx_default_temporal(dsx_temporal_params *t);
+
+/* Validate a parameter set (host only, no device).  Type NONE passes whatever the other fields hold. */
+int dsx_check_temporal(const dsx_temporal_params *t);
+
+/* A[1..max_age] into out[1..max_age], out[0] = 0 (host only); out holds max_age + 1 floats.  Returns the
+ * count max_age + 1; DSX_EINVAL for max_age outside 1..64 or a NULL array. */
+int dsx_temporal_gains(int32_t max_age, float *out);
+
+/* The filter object: it owns the state planes (S, n, h, and two guide planes - the window reads the
+ * neighbours' P while the frame's own G becomes the next P, so the guide state is double-buffered and the
+ * parity is kept here on the host) and the gain table.  A shape change reallocates and resets; otherwise no
+ * call allocates.  Not thread-safe: one caller at a time.
+ *   dsx_tfilter_create      type must be DSX_TEMPORAL_RECURSIVE
+ *   dsx_tfilter_set_params  waits for the filter's last launch, replaces the set and resets the state; on
+ *                           error the filter keeps its old set
+ *   dsx_tfilter_reset       the next frame has no previous frame (no device work)
+ *   dsx_tfilter_bytes       device bytes held */
+typedef struct dsx_tfilter dsx_tfilter;
+int dsx_tfilter_create(int device, const dsx_temporal_params *t, dsx_tfilter **out);
+int dsx_tfilter_set_params(dsx_tfilter *f, const dsx_temporal_params *t);
+int dsx_tfilter_reset(dsx_tfilter *f);
+int dsx_tfilter_bytes(dsx_tfilter *f, int64_t *bytes);
+int dsx_tfilter_destroy(dsx_tfilter *f);
+
+/* One frame: one launch, asynchronous on hip_stream.  d_disp float32 H x W, row pitch in_pitch elements;
+ * d_guide uint8 H x W, row stride guide_stride_bytes; d_out_disp contiguous float32 H x W, which may be d_disp
+ * itself when in_pitch == W (every output reads only its own pixel of d).  Rows of d_disp, d_out_disp and
+ * d_out_depth that are all 16-byte aligned take 16-byte loads and stores; any other pitch or alignment takes
+ * the scalar-per-pixel path.  With d_out_depth non-NULL (contiguous float32 H x W) the same launch writes the
+ * depth of out by the depth map's own rule (dsx_postprocess_fast_device: fB = (float)(focal_length * baseline),
+ * adj = out + doffs, adj > eps ? fB / adj : +inf, clamped to max_depth when has_max_depth); without it the
+ * seven depth scalars are ignored.  H <= 524280.  H == 0 or W == 0: nothing to do.
+ * Frames are filtered in the order of the host's calls: a call on a different stream than the previous one is
+ * ordered behind the previous call's kernel by a stream wait on an event, with no host wait (as
+ * dsx_compute_device orders the users of a handle's scratch), so one filter serves a pipeline that keeps several
+ * frames in flight on several streams.  Argument errors are DSX_EINVAL before any HIP call. */
+#define DSX_TEMPORAL_TILE_W 256 /* pixels of a row per block: 64 lanes x 4 consecutive pixels */
+#define DSX_TEMPORAL_TILE_H 8   /* rows per block                                              */
+int dsx_tfilter_run_device(dsx_tfilter *f, const void *d_disp, int32_t H, int32_t W, int64_t in_pitch,
+                           const void *d_guide, int64_t guide_stride_bytes, void *d_out_disp, void *d_out_depth,
+                           double focal_length, double baseline, double doffs, double eps, double max_depth,
+                           int32_t has_max_depth, void *hip_stream);
 
 /* Per-frame rectification on the device, replacing cv2.cvtColor(BGR2GRAY)
  * + cv2.remap(INTER_LINEAR) of rectify.py:183-186 (cached-maps path) and stereo_core.py:155-159:
