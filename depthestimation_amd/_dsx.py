@@ -50,6 +50,7 @@ EXPORTS = (
     "dsx_default_temporal", "dsx_check_temporal", "dsx_temporal_gains", "dsx_tfilter_create",
     "dsx_tfilter_set_params", "dsx_tfilter_reset", "dsx_tfilter_bytes", "dsx_tfilter_destroy",
     "dsx_tfilter_run_device",
+    "dsx_default_upsample", "dsx_check_upsample", "dsx_upsample_taps", "dsx_upsample_x0", "dsx_upsample_device",
 )
 
 
@@ -158,6 +159,21 @@ class DsxTemporalParams(ctypes.Structure):
     ]
 
 
+UPSAMPLE = {"none": 0, "joint": 1}  # DSX_UPSAMPLE_* (include/dsx.h)
+UPSAMPLE_TILE = (256, 8)  # (DSX_UPSAMPLE_TILE_W, DSX_UPSAMPLE_TILE_H): output pixels per block of the upsampling
+
+
+class DsxUpsample(ctypes.Structure):
+    """dsx_upsample (include/dsx.h): the joint bilateral upsampling of a downscaled run's map."""
+    _fields_ = [
+        ("type", ctypes.c_int32),
+        ("radius", ctypes.c_int32),
+        ("sigma", ctypes.c_int32),
+        ("max_diff", ctypes.c_float),
+        ("reserved", ctypes.c_int32 * 4),
+    ]
+
+
 POST_MODE = {"fast": 1, "full": 2}  # DSX_POST_* (include/dsx.h)
 FILL_METHOD = {"inpaint": 0, "nearest": 1}  # DSX_FILL_* (fill_holes' method names, postprocess.py:72-118)
 NEAREST_PATH = {"auto": 0, "fused": 1, "stepwise": 2}  # DSX_NEAREST_*
@@ -211,7 +227,15 @@ def _bind(lib):
     CL = ctypes.POINTER(DsxCloud)
     TP = ctypes.POINTER(DsxTemporalParams)
     dbl = ctypes.c_double
+    UP = ctypes.POINTER(DsxUpsample)
+    i32p = ctypes.POINTER(i32)
     sig = {
+        "dsx_default_upsample": (None, [UP]),
+        "dsx_check_upsample": (ctypes.c_int, [UP]),
+        "dsx_upsample_taps": (ctypes.c_int, [i32, i32, i32, i32p, i32p]),
+        "dsx_upsample_x0": (i32, [i32, i32, i32]),
+        "dsx_upsample_device": (ctypes.c_int, [vp, i32, i32, i64, i32, vp, i32, i64, vp, i32, i32, i32, i64, UP, vp, vp,
+                                                dbl, dbl, dbl, dbl, dbl, i32, vp]),
         "dsx_default_temporal": (None, [TP]),
         "dsx_check_temporal": (ctypes.c_int, [TP]),
         "dsx_temporal_gains": (ctypes.c_int, [i32, ctypes.POINTER(ctypes.c_float)]),
@@ -466,6 +490,28 @@ def make_temporal(temporal="recursive", max_age=4, max_diff=1.0, motion_radius=1
         raise ValueError("temporal max_diff must be a finite number > 0") from e
     check(lib().dsx_check_temporal(ctypes.byref(t)), "dsx_check_temporal")
     return t
+
+
+def make_upsample(upsample="joint", radius=1, sigma=8, max_diff=1.0) -> DsxUpsample:
+    """dsx_upsample from the stage's keywords; ValueError for an unknown name or a value dsx_check_upsample
+    refuses."""
+    u = DsxUpsample()
+    lib().dsx_default_upsample(ctypes.byref(u))
+    if upsample is None:
+        upsample = "none"
+    if upsample not in UPSAMPLE:
+        raise ValueError(f"upsample must be one of {list(UPSAMPLE)}, got {upsample!r}")
+    u.type = UPSAMPLE[upsample]
+    for name, v in (("radius", radius), ("sigma", sigma)):
+        if isinstance(v, bool) or int(v) != v or abs(int(v)) > 1 << 30:
+            raise ValueError(f"upsample {name} must be an integer")
+        setattr(u, name, int(v))
+    try:
+        u.max_diff = float(max_diff)
+    except (TypeError, ValueError, OverflowError) as e:
+        raise ValueError("upsample max_diff must be a finite number > 0") from e
+    check(lib().dsx_check_upsample(ctypes.byref(u)), "dsx_check_upsample")
+    return u
 
 
 def check_prefilter(p, f: DsxPrefilter) -> None:

@@ -1014,3 +1014,62 @@ class TemporalFilterDevice:
             self.close()
         except Exception:
             pass
+
+
+def joint_upsample_device(disp, x0, guide_lo, guide, radius=1, sigma=8, max_diff=1.0, focal_length=None,
+                          baseline=None, doffs=0.0, eps=1e-6, max_depth=None, out=None, out_depth=None, stream=None):
+    """The joint bilateral upsampling of a downscaled run's map on the device (dsx_upsample_device; host
+    restatement upsample.joint_upsample, equal bit for bit).  ``disp``: the finished float32 h x w HIP tensor whose
+    column 0 is low-resolution column ``x0``; ``guide_lo``: the uncropped uint8 h x Wl low-resolution image the
+    matcher ran on (Wl = x0 + w); ``guide``: the full-size uint8 frame, H x W or H x W x 3 (the kernel forms the
+    gray value).  All with unit element stride along a row, any row stride or offset.  Returns ``(out, depth)``:
+    contiguous float32 H x (W - X0) tensors, the disparity in full-size pixels and, with ``focal_length`` and
+    ``baseline`` (the low-resolution calibration), the metric depth written by the same launch; else None.
+    Stateless, asynchronous on ``stream``."""
+    import torch
+
+    if not hasattr(disp, "dtype") or disp.dtype != torch.float32 or disp.dim() != 2 or not disp.is_cuda or \
+            (disp.shape[1] > 1 and disp.stride(1) != 1):
+        raise ValueError("disp must be a float32 h x w device tensor with unit column stride")
+    if not hasattr(guide_lo, "dtype") or guide_lo.dtype != torch.uint8 or guide_lo.dim() != 2 or \
+            guide_lo.device != disp.device or guide_lo.shape[0] != disp.shape[0] or \
+            (guide_lo.shape[1] > 1 and guide_lo.stride(1) != 1):
+        raise ValueError("guide_lo must be a uint8 h x Wl tensor on disp's device with unit column stride")
+    if not hasattr(guide, "dtype") or guide.dtype != torch.uint8 or guide.dim() not in (2, 3) or \
+            guide.device != disp.device or (guide.dim() == 3 and guide.shape[2] not in (1, 3)):
+        raise ValueError("guide must be a uint8 H x W or H x W x 3 tensor on disp's device")
+    ch = 1 if guide.dim() == 2 else int(guide.shape[2])
+    H, W = int(guide.shape[0]), int(guide.shape[1])
+    if guide.dim() == 3 and (guide.stride(2) != 1 or (W > 1 and guide.stride(1) != ch)):
+        raise ValueError("guide must have its channels interleaved (unit element stride along a row)")
+    if guide.dim() == 2 and W > 1 and guide.stride(1) != 1:
+        raise ValueError("guide must have unit column stride")
+    h, w = int(disp.shape[0]), int(disp.shape[1])
+    Wl, x0 = int(guide_lo.shape[1]), int(x0)
+    if x0 < 0 or x0 + w != Wl:
+        raise ValueError("disp must cover the low-resolution columns x0 .. Wl - 1 (x0 + w == Wl)")
+    if not (1 <= h <= H <= 32768 and 1 <= Wl <= W <= 32768):
+        raise ValueError("shapes must satisfy 1 <= h <= H <= 32768 and 1 <= Wl <= W <= 32768")
+    up = _dsx.make_upsample("joint", radius, sigma, max_diff)
+    X0 = _dsx.lib().dsx_upsample_x0(W, Wl, x0)
+    _dsx.check(min(X0, 0), "dsx_upsample_x0")
+    dev = _device_index(disp)
+    shape = (H, W - X0)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=disp.device)
+    _check_out(out, shape, "torch.float32", dev, "out")
+    want_depth = focal_length is not None and baseline is not None
+    if want_depth and out_depth is None:
+        out_depth = torch.empty(shape, dtype=torch.float32, device=disp.device)
+    if want_depth:
+        _check_out(out_depth, shape, "torch.float32", dev, "out_depth")
+    if w == 0 or shape[1] == 0:
+        return out, (out_depth if want_depth else None)
+    rc = _dsx.lib().dsx_upsample_device(
+        disp.data_ptr(), h, w, max(disp.stride(0), w) if h > 1 else w, x0, guide_lo.data_ptr(), Wl,
+        max(guide_lo.stride(0), Wl) if h > 1 else Wl, guide.data_ptr(), H, W, ch,
+        max(guide.stride(0), W * ch) if H > 1 else W * ch, ctypes.byref(up), _ptr(out),
+        _ptr(out_depth) if want_depth else None, float(focal_length or 0.0), float(baseline or 0.0),
+        float(doffs or 0.0), float(eps), float(max_depth or 0.0), int(max_depth is not None), _stream_ptr(stream))
+    _dsx.check(rc, "dsx_upsample_device")
+    return out, (out_depth if want_depth else None)

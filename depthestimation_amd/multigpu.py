@@ -349,7 +349,10 @@ class DepthPipeline:
     'temporal': 'recursive' is honoured: the per-slot copies of the core share its one temporal filter, which
     every frame calls in push order on the frame's own stream; the library orders each call behind the previous
     frame's filter launch (an event between the streams, no host wait), so the frames are filtered in order
-    while frame i + 1's matcher still overlaps frame i.  Frames must be pushed in sequence order."""
+    while frame i + 1's matcher still overlaps frame i.  Frames must be pushed in sequence order.
+
+    'upsample': 'joint' is honoured with ``input_scale``: every frame's depth map comes back at the full size
+    of the pushed frames, H x (W - X0) (upsample.py), written by the upsampling launch on the frame's stream."""
 
     def __init__(self, core, device: int, depth: int = 3, streams: int = 2, input_scale=None):
         import copy

@@ -75,6 +75,23 @@ Keys added to ``sgbm_params`` (accepted by ``configure_sgbm`` like the reference
                                        'temporal_max_diff' > 0 px (1.0), 'temporal_motion_radius' 0..2 (1),
                                        'temporal_motion_threshold' 0..255 grey levels per tap (6),
                                        'temporal_hold' 0..255 frames (2))
+  'upsample': 'none' | 'joint'        ('none', the default.  'joint': full-resolution output for downscaled runs -
+                                       the joint bilateral upsampling of upsample.py.  It runs only in calls that
+                                       carry ``input_scale`` != 1 (``estimate_depth`` / ``estimate_depth_device``, and
+                                       through them the facades with ``device_downscale=True`` and
+                                       ``DepthPipeline(input_scale=...)``), behind the mode's tail and behind the
+                                       temporal filter, which keeps working and keeping its state at low resolution:
+                                       one launch reads the finished low-resolution map, the low-resolution left
+                                       image and the full-size left frame and writes ``disparity_map`` in full-size
+                                       pixels and ``depth_map``, both H x (W - X0) with X0 = upsample.upsample_x0(W,
+                                       Wl, num_disp).  Without ``input_scale`` the key is ignored, as fast mode
+                                       ignores 'hole_filling': there is no full-size frame.  With a full calibration
+                                       the call raises ValueError: rectification runs after the downscale, so the
+                                       full-size frame is not rectified and cannot guide.  ``confidence_map`` stays
+                                       low-resolution; ``point_cloud`` after an upsampled frame raises ValueError
+                                       (its intrinsics and crop are the low-resolution ones).  'upsample_radius'
+                                       1..3 (1), 'upsample_sigma' 1..64 grey levels (8), 'upsample_max_diff' > 0
+                                       low-resolution px (1.0))
 Keys of the reference that have no block-matching meaning are kept, validated and reported
 but do not change the result: 'prefilter_cap' unless 'cost' is 'bt' or a prefilter is set, 'speckle_window_size' /
 'speckle_range' unless 'sgbm_post' is set, and 'sgbm_mode' / P1 / P2 while 'aggregation' is 'none'
@@ -90,11 +107,12 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 
 from .input import resize_area, resize_area_device
-from .matcher import (HipBlockMatcher, TemporalFilterDevice, default_workspace, fill_holes_status, postprocess_fast_device,
-                      point_cloud_device, postprocess_full_device, rectify_device)
+from .matcher import (HipBlockMatcher, TemporalFilterDevice, default_workspace, fill_holes_status, joint_upsample_device,
+                      postprocess_fast_device, point_cloud_device, postprocess_full_device, rectify_device)
 from .pointcloud import point_cloud as host_point_cloud
 from .postprocess import median_blur3, postprocess_disparity
 from .temporal import TemporalFilter, check_temporal
+from .upsample import check_upsample, joint_upsample
 from .rectify import RectificationCache, rectified_principal_point, rectify_images, to_grayscale_bgr
 
 _SGBM_MODES = ("sgbm", "hh", "sgbm_3way", "hh4")
@@ -234,8 +252,13 @@ class StereoCore:
             'temporal_motion_radius': 1,
             'temporal_motion_threshold': 6,
             'temporal_hold': 2,
+            'upsample': 'none',
+            'upsample_radius': 1,
+            'upsample_sigma': 8,
+            'upsample_max_diff': 1.0,
         }
         self._temporal = None
+        self._upsampled = False  # the last frame's maps are full-size (point_cloud refuses them)
         self._pp_cache = None  # (calibration key, (cx, cy) of the left rectified image)
         self.confidence_map = None
         self._build_sgbm()
@@ -280,6 +303,19 @@ class StereoCore:
             check_temporal(max_diff=tkw['max_diff'])
         except ValueError:
             raise ValueError("Invalid parameter value for 'temporal_max_diff': expected a finite number > 0") from None
+        if p.get('upsample', 'none') not in ('none', 'joint'):
+            raise ValueError("Invalid parameter value for 'upsample': expected 'none' or 'joint'")
+        ukw = self._upsample_kwargs()
+        for key, (lo, hi) in (('radius', (1, 3)), ('sigma', (1, 64))):
+            try:
+                check_upsample(**{key: ukw[key]})
+            except ValueError:
+                raise ValueError(f"Invalid parameter value for 'upsample_{key}': expected an integer in "
+                                 f"[{lo}, {hi}]") from None
+        try:
+            check_upsample(max_diff=ukw['max_diff'])
+        except ValueError:
+            raise ValueError("Invalid parameter value for 'upsample_max_diff': expected a finite number > 0") from None
         # any (re)configuration forgets the temporal state; the filter objects are built on first use
         if getattr(self, '_temporal', None) is not None:
             self._temporal.close()
@@ -344,6 +380,29 @@ class StereoCore:
                     motion_radius=p.get('temporal_motion_radius', 1),
                     motion_threshold=p.get('temporal_motion_threshold', 6), hold=p.get('temporal_hold', 2))
 
+    def _upsample_kwargs(self) -> dict:
+        """The 'upsample_*' keys as the keywords of joint_upsample / joint_upsample_device."""
+        p = self.sgbm_params
+        return dict(radius=p.get('upsample_radius', 1), sigma=p.get('upsample_sigma', 8),
+                    max_diff=p.get('upsample_max_diff', 1.0))
+
+    def _depth_kwargs(self) -> dict:
+        """The depth scalars as the upsampling launch takes them (the low-resolution calibration)."""
+        p = self.sgbm_params
+        return dict(focal_length=p.get('focal_length'), baseline=p.get('baseline'), doffs=p.get('doffs', 0.0),
+                    eps=p.get('min_disp', 5.0), max_depth=p.get('max_depth'))
+
+    def _upsample_on(self, input_scale) -> bool:
+        """The stage runs in this call: 'upsample': 'joint' and an ``input_scale`` other than 1.  ValueError with
+        a full calibration set."""
+        p = self.sgbm_params
+        if p.get('upsample', 'none') != 'joint' or input_scale is None or input_scale == 1.0:
+            return False
+        if all(p.get(k) is not None for k in _CALIBRATION_KEYS):
+            raise ValueError("'upsample': 'joint' cannot run with a full calibration: rectification runs after the "
+                             "downscale, so the full-size frame is not rectified and cannot guide the upsampling")
+        return True
+
     def reset_temporal(self) -> None:
         """Forget the temporal filter's state: the next frame is filtered as a first frame (a scene cut)."""
         if self._temporal is not None:
@@ -368,9 +427,13 @@ class StereoCore:
             right_img = to_grayscale_bgr(right_img)
         return left_img, right_img
 
-    def _process_pair(self, left_img: np.ndarray, right_img: np.ndarray) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+    def _process_pair(self, left_img: np.ndarray, right_img: np.ndarray,
+                      full_guide=None) -> Tuple[np.ndarray, Optional[np.ndarray]]:
         """stereo_core.py:162-200: disparity -> crop [:, num_disp:] -> median (fast) or
-        postprocess -> depth when focal length and baseline are set."""
+        postprocess -> depth when focal length and baseline are set.  ``full_guide``: the full-size left frame of
+        a call with ``input_scale`` and 'upsample': 'joint' - the maps are then upsampled to it (upsample.py)."""
+        raw_left = np.asarray(left_img)
+        self._upsampled = False
         if self.sgbm_params.get('confidence', False) and 'compute_disparity' not in self.__dict__:
             if self.sgbm is None:
                 self._build_sgbm()
@@ -407,7 +470,13 @@ class StereoCore:
         min_disparity = self.sgbm_params.get('min_disp', 5.0)
         max_depth = self.sgbm_params.get('max_depth')
         depth_m = None
-        if f_pixels is not None and baseline_m is not None:
+        if full_guide is not None:  # the upsampling writes the depth of the unscaled average
+            disparity_px, depth_m = joint_upsample(np.ascontiguousarray(disparity_px, np.float32),
+                                                   min(self.sgbm_params['num_disp'], raw_left.shape[1]), raw_left,
+                                                   full_guide,
+                                                   **self._upsample_kwargs(), **self._depth_kwargs())
+            self._upsampled = True
+        elif f_pixels is not None and baseline_m is not None:
             depth_m = self.disparity_to_depth(disparity_px, f_pixels, baseline_m, doffs, eps=min_disparity,
                                               max_depth=max_depth)
         self.disparity_map = disparity_px
@@ -465,21 +534,33 @@ class StereoCore:
         Equal bit for bit to passing ``resize_area(frame, input_scale)``."""
         if left_source is None or right_source is None:
             raise ValueError("Left and right sources must be set before estimating depth.")
+        full_guide = left_source if self._upsample_on(input_scale) else None
         if input_scale is not None and input_scale != 1.0:
             left_source = resize_area_device(left_source, input_scale, gray=left_source.dim() == 3, stream=stream)
             right_source = resize_area_device(right_source, input_scale, gray=right_source.dim() == 3, stream=stream)
         self.left_rectified, self.right_rectified = self._prepare_rectified_device(left_source, right_source, stream)
-        return self.process_pair_device(self.left_rectified, self.right_rectified, stream=stream)
+        return self.process_pair_device(self.left_rectified, self.right_rectified, stream=stream, full_guide=full_guide)
 
-    def process_pair_device(self, left, right, stream=None):
+    def process_pair_device(self, left, right, stream=None, full_guide=None):
         """Device-resident ``_process_pair`` (stereo_core.py:162-200) for rectified uint8 HIP
         tensors: matcher -> crop -> post-processing -> depth, all in HBM.  Fast mode: 3x3 median
         (SURVEY.md 8f row F1); otherwise speckle filter + outlier removal (+ hole filling
         with ``hole_filling``, by ``fill_method``; + the guided weighted median with ``refine``, guided
         by ``left``) + median (row F2).  Returns float32 HIP tensors
-        (disparity_px, depth_m or None)."""
+        (disparity_px, depth_m or None).  ``full_guide``: the full-size left frame (uint8, H x W or H x W x 3) of a
+        call with ``input_scale`` and 'upsample': 'joint': the chain and the temporal filter then run without
+        depth scalars, and the upsampling launch writes the full-size disparity and the depth."""
         p = self.sgbm_params
-        f, B = p.get('focal_length'), p.get('baseline')
+        self._upsampled = full_guide is not None
+        if full_guide is not None:
+            d, _ = self._process_pair_lowres_device(left, right, stream, None, None)
+            return joint_upsample_device(d, min(p['num_disp'], left.shape[1]), left, full_guide, stream=stream,
+                                         **self._upsample_kwargs(), **self._depth_kwargs())
+        return self._process_pair_lowres_device(left, right, stream, p.get('focal_length'), p.get('baseline'))
+
+    def _process_pair_lowres_device(self, left, right, stream, f, B):
+        """``process_pair_device`` at the matcher's resolution (depth when ``f`` and ``B``)."""
+        p = self.sgbm_params
         doffs, eps, max_depth = p.get('doffs', 0.0), p.get('min_disp', 5.0), p.get('max_depth')
         fill = bool(p.get('hole_filling', False)) and not self.fast_mode
         method = p.get('fill_method', 'inpaint')
@@ -578,6 +659,11 @@ class StereoCore:
         return dict(focal_length=f, baseline=B, principal_point=self.resolve_principal_point(height, x0 + width),
                     doffs=p.get('doffs', 0.0), eps=p.get('min_disp', 5.0), max_depth=p.get('max_depth'), x0=x0)
 
+    def _refuse_upsampled_cloud(self) -> None:
+        if self._upsampled:
+            raise ValueError("point_cloud cannot reproject an upsampled frame: its intrinsics and crop are the "
+                             "low-resolution ones (run with 'upsample': 'none' for a cloud)")
+
     def point_cloud(self, colors=None):
         """The last frame's ``disparity_map`` as a point cloud: ``(points, colors, index)`` host arrays -
         float32 N x 3 metric XYZ (x right, y down, z forward) of the valid pixels in row-major order, uint8
@@ -593,6 +679,7 @@ class StereoCore:
         disp = self.disparity_map
         if disp is None:
             raise ValueError("No frame has been processed: call estimate_depth first.")
+        self._refuse_upsampled_cloud()
         disp = np.asarray(disp, np.float32)
         H, W = disp.shape
         kw = self._cloud_kwargs(H, W)
@@ -622,6 +709,7 @@ class StereoCore:
         rectified left image of the last device frame, if it has the frame's size).  Returns what
         matcher.point_cloud_device returns: with ``sync`` the exact-length tensors, without it the
         full-capacity tensors and the count tensor, with no host synchronisation."""
+        self._refuse_upsampled_cloud()
         H, W = disp.shape
         kw = self._cloud_kwargs(H, W)
         if colors is None:
@@ -654,6 +742,12 @@ class StereoCore:
         if input_scale is not None and input_scale == 1.0:
             input_scale = None
         if input_scale is not None and not self._device_pipeline_ok(left_source, right_source, input_scale):
+            if self._upsample_on(input_scale):
+                self.left_rectified, self.right_rectified = self._prepare_rectified(
+                    resize_area(np.ascontiguousarray(left_source), input_scale),
+                    resize_area(np.ascontiguousarray(right_source), input_scale))
+                return self._process_pair(self.left_rectified, self.right_rectified,
+                                          full_guide=np.ascontiguousarray(left_source))
             return self.estimate_depth(resize_area(np.ascontiguousarray(left_source), input_scale),
                                        resize_area(np.ascontiguousarray(right_source), input_scale))
         if self._device_pipeline_ok(left_source, right_source, input_scale):

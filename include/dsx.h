@@ -32,7 +32,10 @@
 extern "C" {
 #endif
 
-#define DSX_VERSION 106 /* additive since 1.0.6 (layouts unchanged): dsx_temporal_params, dsx_default_temporal,
+#define DSX_VERSION 106 /* additive since 1.0.6 (layouts unchanged): dsx_upsample, dsx_default_upsample,
+                           dsx_check_upsample, dsx_upsample_taps, dsx_upsample_x0, dsx_upsample_device
+                           (joint bilateral upsampling of a downscaled run's map to the full-size frame);
+                           dsx_temporal_params, dsx_default_temporal,
                            dsx_check_temporal, dsx_temporal_gains, dsx_tfilter_create, dsx_tfilter_set_params,
                            dsx_tfilter_reset, dsx_tfilter_destroy, dsx_tfilter_bytes, dsx_tfilter_run_device
                            (temporal disparity filter for video: motion-gated recursive average);
@@ -667,6 +670,83 @@ int dsx_tfilter_run_device(dsx_tfilter *f, const void *d_disp, int32_t H, int32_
                            const void *d_guide, int64_t guide_stride_bytes, void *d_out_disp, void *d_out_depth,
                            double focal_length, double baseline, double doffs, double eps, double max_depth,
                            int32_t has_max_depth, void *hip_stream);
+
+/* Full-resolution output for downscaled runs: joint bilateral upsampling.  An addition of this build (as the
+ * prefilter, the census costs, the refinement, the point cloud and the temporal filter are): parity with nothing
+ * outside this repository is claimed.  A run with an input downscale matches at h x Wl pixels; this stage brings
+ * its finished map back to the H x W frame the caller holds, guided by that frame, in one stateless launch.
+ * Inputs:
+ *   d  the finished low-resolution float32 map, h x w, row pitch in elements; its column 0 is low-resolution
+ *      image column x0 (the crop: num_disp for the maps of the chain), so x0 + w == Wl;
+ *   g  the low-resolution uint8 guide, h x Wl, UNCROPPED, row stride in bytes, any alignment: the raw left image
+ *      the matcher ran on, also when a prefilter is set;
+ *   G  the full-size uint8 guide, H x W x ch, ch 1 or 3, row stride in bytes, any alignment.  For ch = 3 the
+ *      kernel forms the gray value itself, (c0 * 1868 + c1 * 9617 + c2 * 4899 + 8192) >> 14 in memory order (the
+ *      formula of dsx_rectify_device / dsx_resize_area_device); no full-size gray image is written anywhere.
+ *   1 <= h <= H, 1 <= Wl <= W, H, W <= 32768.
+ * Geometry, per axis with hi-res size I and low-res size O <= I, in integers only:
+ *   near(X)    = ((2X + 1) O) div (2 I): the low-res pixel whose cell contains hi-res centre X (<= O - 1);
+ *   tap        k = near(X) + t - r, t = 0..2r;  n = |(2X + 1) O - (2k + 1) I|;
+ *   tent       a(X, t) = max(0, 64 - ((64 n + (r + 1) I) div (2 (r + 1) I)))      (the centre tap's is > 0);
+ *   X0         = max(0, ceil((2 W x0 - Wl) / (2 Wl))): the smallest X with near_x(X) >= x0.
+ * The output covers hi-res columns X0 .. W - 1 and all H rows: H x (W - X0), contiguous.  W - X0 <= 0 or w = 0:
+ * nothing to do.
+ * Per output pixel P = (X, Y), r = radius:
+ *   window     y = near_y(Y) + j - r, x = near_x(X) + i - r, j outer and i inner, each 0..2r; taps with y outside
+ *              [0, h) or x - x0 outside [0, w) are skipped;
+ *   validity   a tap is valid iff 0 < d(y, x - x0) < +inf (the refinement's rule);
+ *   weight     W_q = a_x(X, i) a_y(Y, j) T[|G(P) - g(y, x)|] <= 2^20, T the refinement's table
+ *              dsx_wmedian_weights(sigma), built on the host;
+ *   selection  S = the sum of W_q over the valid taps; m = the smallest valid tap value v with
+ *              2 (sum of W_q over d_q <= v) >= S;
+ *   average    float32, every operation correctly rounded, no FMA: over the valid taps with |d_q - m| <= max_diff
+ *              in window order num <- num + ((float)W_q * d_q); den = the integer sum of their W_q, converted
+ *              once; a = num / den (the selected tap itself has W_q >= 1, so den >= 1);
+ *   outputs    out_disp(P) = a * sx, sx = (float)((double)W / (double)Wl): full-size pixels;
+ *              out_depth(P) = the depth of the UNSCALED a by the depth map's own rule (dsx_postprocess_fast_device:
+ *              fB = (float)(focal_length * baseline), adj = a + doffs, adj > eps ? fB / adj : +inf, clamped to
+ *              max_depth) - metric depth does not depend on the resolution, so the scalars are the
+ *              low-resolution calibration's;
+ *   no valid tap: out_disp(P) = the bits of d(near_y(Y), near_x(X) - x0) unchanged - invalid by construction,
+ *              unscaled - and the depth rule applied to that value.
+ * Host restatement: depthestimation_amd/upsample.py joint_upsample, equal bit for bit. */
+#define DSX_UPSAMPLE_NONE 0
+#define DSX_UPSAMPLE_JOINT 1
+typedef struct dsx_upsample {
+    int32_t type;   /* DSX_UPSAMPLE_* (JOINT)                                                   */
+    int32_t radius; /* 1..3 (1): the window is (2 radius + 1)^2 low-resolution taps              */
+    int32_t sigma;  /* 1..64 grey levels (8)                                                    */
+    float max_diff; /* finite, > 0, LOW-RESOLUTION pixels (1.0): the gate of the average around m */
+    int32_t reserved[4];
+} dsx_upsample;
+
+/* joint, radius 1, sigma 8, max_diff 1.0 */
+void dsx_default_upsample(dsx_upsample *u);
+
+/* Validate a parameter set (host only, no device).  Type NONE passes whatever the other fields hold. */
+int dsx_check_upsample(const dsx_upsample *u);
+
+/* The integer geometry of one axis (host only): near[X] and tent[X * (2 radius + 1) + t] for X = 0..in_size - 1
+ * (in_size the hi-res size I, out_size the low-res size O).  DSX_EINVAL unless 1 <= out_size <= in_size <= 32768,
+ * radius in 1..3 and both arrays non-NULL. */
+int dsx_upsample_taps(int32_t in_size, int32_t out_size, int32_t radius, int32_t *near, int32_t *tent);
+
+/* X0 of the geometry above (host only); DSX_EINVAL unless 1 <= Wl <= W <= 32768 and 0 <= x0 <= Wl. */
+int32_t dsx_upsample_x0(int32_t W, int32_t Wl, int32_t x0);
+
+/* The launch.  d_out_disp / d_out_depth: contiguous float32 H x (W - X0); d_out_depth NULL: no depth, and the
+ * seven depth scalars are ignored.  Output rows that are 16-byte aligned (W - X0 a multiple of 4, aligned bases)
+ * take 16-byte stores, any other shape the scalar path.  Stateless: one launch, asynchronous on hip_stream, no
+ * workspace, no grid barrier, no status flag.  Argument errors are DSX_EINVAL before any HIP call: NULL arguments,
+ * Wl > W, h > H, x0 < 0, x0 + w != Wl, pitches or strides too small, channels other than 1 or 3,
+ * d_out_disp == d_disp. */
+#define DSX_UPSAMPLE_TILE_W 256 /* output pixels of a row per block: 64 lanes x 4 consecutive pixels */
+#define DSX_UPSAMPLE_TILE_H 8   /* output rows per block                                             */
+int dsx_upsample_device(const void *d_disp, int32_t h, int32_t w, int64_t in_pitch, int32_t x0, const void *d_guide_lo,
+                        int32_t Wl, int64_t guide_lo_stride_bytes, const void *d_guide, int32_t H, int32_t W,
+                        int32_t channels, int64_t guide_stride_bytes, const dsx_upsample *params, void *d_out_disp,
+                        void *d_out_depth, double focal_length, double baseline, double doffs, double eps,
+                        double max_depth, int32_t has_max_depth, void *hip_stream);
 
 /* Per-frame rectification on the device, replacing cv2.cvtColor(BGR2GRAY)
  * + cv2.remap(INTER_LINEAR) of rectify.py:183-186 (cached-maps path) and stereo_core.py:155-159:
