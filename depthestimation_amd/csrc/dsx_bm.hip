@@ -43,61 +43,19 @@
 constexpr int kWpe = 3;     // waves per SIMD the fused pass is compiled for (SAD, and SSD below 4 waves)
 constexpr int kWpeSsd = 4;  // SSD blocks of >= 4 waves
 
-// Row-step forms that can be switched off for an A/B build (tools/variant_bm.sh -DDSX_ROWSTEP_ATID=0
-// / -DDSX_ROWSTEP_KEY2=0 / -DDSX_ROWSTEP_MERGE=0): the lane-indexed tile stores, the key-tree argmin and the
-// merged row staging of the pair layout; -DDSX_ROWSTEP_DIVQ=0: the branch-free sub-pixel quotient of the left
-// tail.  -DDSX_ROWSTEP_PAIRTAIL=1 switches ON the left tail once per two rows, which is off by default: it issues
-// 2.7 % fewer VALU ops per C2 launch and ran 1 % slower than the build without it.
-#ifndef DSX_ROWSTEP_PAIRTAIL
-#define DSX_ROWSTEP_PAIRTAIL 0
-#endif
-#ifndef DSX_ROWSTEP_DIVQ
-#define DSX_ROWSTEP_DIVQ 1
-#endif
-// -DDSX_ROWSTEP_OVERLAP=0 / -DDSX_ROWSTEP_AHEAD=0: the rotated row loop (row y - 1's epilogue issued between the
-// chunks of row y's column update) and the column update's LDS reads one chunk ahead (OVL / AHD in bm2_segment).
-#ifndef DSX_ROWSTEP_OVERLAP
-#define DSX_ROWSTEP_OVERLAP 1
-#endif
-#ifndef DSX_ROWSTEP_AHEAD
-#define DSX_ROWSTEP_AHEAD 1
-#endif
-// -DDSX_ROWSTEP_SREF=1 switches ON the reference row of the rotated loop's unaligned-dword copy through the scalar
-// unit (SREF in bm2_segment) instead of broadcast LDS reads, which is off by default: the C2 loop then holds 20
-// ds_read_b128 and 4 VALU fewer per step, spills nothing, and ran 10 % slower (one-stream kernel 51.3 -> 56.7 us,
-// 44.8k -> 41.2k Mpix/s with three frames in flight; DESIGN 4.4, profiles/sref_ab.txt).  -DDSX_ROWSTEP_SARGS
-// (default: as SREF) is its second half on its own switch: the stages behind the last chunk re-read their launch
-// arguments, which frees the SGPRs the dwords need; alone it costs 0.3 us.
-#ifndef DSX_ROWSTEP_SREF
-#define DSX_ROWSTEP_SREF 0
-#endif
-#ifndef DSX_ROWSTEP_SARGS
-#define DSX_ROWSTEP_SARGS DSX_ROWSTEP_SREF
-#endif
-// The rotated loop holds row y - 1's two output stores behind step y's last chunk, and the staging of step y + 1's
-// rows behind the box phase then waits with vmcnt(1) / (0) behind them: vmcnt counts loads and stores in order, so
-// each step drained its stores.  Two orders avoid that, each on its own switch (profiles/stageahead_ab.txt):
-// -DDSX_ROWSTEP_STORELATE=0 restores the stores behind the last chunk.  With it (STL in bm2_segment, default) the tail
-// forms the two outputs where it did and issues the stores at the end of the step, behind the staging; the loads
-// keep the whole step to land.  C2 with three frames in flight 47,214 -> 47,567 Mpix/s (+0.7 %, every run above
-// every parent run).
-// -DDSX_ROWSTEP_STAGEAHEAD=1 switches ON the staging directly behind the last chunk, in front of the stores (STA),
-// which is off by default: the loads then have only the column update to land, SQ_WAIT_ANY per C2 launch rose
-// 16.12 M -> 16.54 M and the step ran 1.0 % slower than the parent's (46,884 against 47,342 Mpix/s).
-#ifndef DSX_ROWSTEP_STAGEAHEAD
-#define DSX_ROWSTEP_STAGEAHEAD 0
-#endif
-constexpr bool kRowstepStageahead = DSX_ROWSTEP_STAGEAHEAD;  // the loops that run OVL
-#ifndef DSX_ROWSTEP_STORELATE
-#define DSX_ROWSTEP_STORELATE 1
-#endif
-constexpr bool kRowstepStorelate = DSX_ROWSTEP_STORELATE;  // the loops that run OVL
-constexpr bool kRowstepSref = DSX_ROWSTEP_SREF;          // pair layout, one-wave left pass, R <= 4
-constexpr bool kRowstepSargs = DSX_ROWSTEP_SARGS;        // the same loops: launch arguments re-read behind the last chunk
-constexpr bool kRowstepOverlap = DSX_ROWSTEP_OVERLAP;    // pair layout, one-wave left pass, R <= 5
-constexpr bool kRowstepAhead = DSX_ROWSTEP_AHEAD;        // pair layout, one-wave left pass, R <= 5
-constexpr bool kRowstepPairtail = DSX_ROWSTEP_PAIRTAIL;  // pair layout, one-wave left pass
-constexpr bool kRowstepDivq = DSX_ROWSTEP_DIVQ;          // pair layout, left pass
+// Compile-time switches of bm2_segment, each =1 by default; =0 restores the previous form, which other sides and
+// radii still run, for an A/B build (tools/variant_bm.sh -D<SWITCH>=0; tools/isa_same.py compares the code objects).
+//   DSX_ROWSTEP_ATID      lane-indexed tile stores of the pair layout outside the LR pass
+//   DSX_ROWSTEP_KEY2      key argmin of the pair layout's left pass up to R = 5; the rotated row loop needs it
+//                         
+//   DSX_ROWSTEP_MERGE     merged row staging, one load and one 16-B store per staged row (MRG)
+//   DSX_ROWSTEP_COLGROUP  3-column group sums of the 9x9 and 3x3 rotated loops (CG; DESIGN 4.1,
+//                         profiles/colgroup_isa.txt)
+//   DSX_SEGSTART_AHEAD    transposed init: chunk q + 1's LDS reads in front of chunk q's SADs (IAH)
+//   DSX_SEGSTART_BATCH    transposed init: every row's loads in one batch ahead of the transposes (IBT)
+// Removed, last present in commit 70ab923 (measurements: DESIGN 4.4, profiles/*_ab.txt): the rejected forms
+// DSX_ROWSTEP_PAIRTAIL, DSX_ROWSTEP_SREF, DSX_ROWSTEP_SARGS, DSX_ROWSTEP_STAGEAHEAD, DSX_SEGSTART_SPART and
+// DSX_SEGSTART_ROW0; folded to on: DSX_ROWSTEP_OVERLAP, DSX_ROWSTEP_AHEAD, DSX_ROWSTEP_STORELATE, DSX_ROWSTEP_DIVQ.
 #ifndef DSX_ROWSTEP_ATID
 #define DSX_ROWSTEP_ATID 1
 #endif
@@ -107,49 +65,21 @@ constexpr bool kRowstepDivq = DSX_ROWSTEP_DIVQ;          // pair layout, left pa
 #ifndef DSX_ROWSTEP_MERGE
 #define DSX_ROWSTEP_MERGE 1
 #endif
-constexpr bool kRowstepMerge = DSX_ROWSTEP_MERGE;  // one load and one 16-B store per staged row
-// -DDSX_ROWSTEP_COLGROUP=0 restores the single-column sums of the 9x9 and 3x3 rotated loops (CG in bm2_segment): with
-// it the unaligned-dword copy of bm2<4, SAD, 1, 0> and bm2<1, SAD, 1, 0> keeps, per column c, the sum of columns c,
-// c + 1 and c + 2 over the live rows.  The staged words are 3-byte windows, so one v_sad_u8 adds a whole entering or
-// leaving 3-column term, and a 9-column box is one v_add3_u32 of three group sums (profiles/colgroup_isa.txt).
 #ifndef DSX_ROWSTEP_COLGROUP
 #define DSX_ROWSTEP_COLGROUP 1
 #endif
-constexpr bool kRowstepColgroup = DSX_ROWSTEP_COLGROUP;
-constexpr bool kRowstepAtid = DSX_ROWSTEP_ATID;
-constexpr bool kRowstepKey2 = DSX_ROWSTEP_KEY2;
-// Segment-start forms (the code between kernel entry and a segment's first row step), each behind its own switch
-// for an A/B build; =0 restores the previous form.
-// -DDSX_SEGSTART_AHEAD=0: the transposed init's SAD loop reads chunk q + 1's LDS words in front of chunk q's SADs
-// (two register sets; only a row group's first chunk waits with a full drain) instead of one drain per read.
-// -DDSX_SEGSTART_BATCH=0: the transposed init's row loads of the unaligned-dword copy up to R = 4 are issued in one
-// batch ahead of the transposes, all 2R+1 rows and unconditionally (rows past 2R are compile-time zeros), instead
-// of one global round trip per row group.
-// -DDSX_SEGSTART_SPART=1 switches ON the block's two partition words through scalar loads issued at kernel entry, in
-// front of the invalid-band fill and the LR key reset, instead of two vector loads behind them; off by default: alone
-// it ran the C2 step 0.11 us slower than the parent (44.44 against 44.33 us, spread 0.07), and next to the other two
-// it was within the spread (43.46 against 43.54 us; DESIGN 4.4, profiles/segstart_ab.txt).
 #ifndef DSX_SEGSTART_AHEAD
 #define DSX_SEGSTART_AHEAD 1
 #endif
 #ifndef DSX_SEGSTART_BATCH
 #define DSX_SEGSTART_BATCH 1
 #endif
-#ifndef DSX_SEGSTART_SPART
-#define DSX_SEGSTART_SPART 0
-#endif
-// -DDSX_SEGSTART_ROW0=1 switches ON the first step's two prefetch loads in front of the init SAD loop (SR0 in
-// bm2_segment): the batched-init builds of the merged staging hold the two dwords across that loop, and step yb, whose
-// body is only the box phase, issues no prefetch of its own; its rows are staged in front of the row loop.  Off by
-// default: alone it ran C2 0.5 % below the parent (47,117 against 47,342 Mpix/s, spreads 0.2 - 0.5 %), next to
-// STAGEAHEAD 0.4 % above it, next to STORELATE 2.1 % below it.
-#ifndef DSX_SEGSTART_ROW0
-#define DSX_SEGSTART_ROW0 0
-#endif
-constexpr bool kSegstartRow0 = DSX_SEGSTART_ROW0;
+constexpr bool kRowstepAtid = DSX_ROWSTEP_ATID;
+constexpr bool kRowstepKey2 = DSX_ROWSTEP_KEY2;
+constexpr bool kRowstepMerge = DSX_ROWSTEP_MERGE;
+constexpr bool kRowstepColgroup = DSX_ROWSTEP_COLGROUP;
 constexpr bool kSegstartAhead = DSX_SEGSTART_AHEAD;
 constexpr bool kSegstartBatch = DSX_SEGSTART_BATCH;
-constexpr bool kSegstartSpart = DSX_SEGSTART_SPART;
 
 #include <algorithm>
 #include <cstdio>
@@ -316,12 +246,8 @@ __device__ __forceinline__ uint32_t gmin(uint32_t v) {
 }
 
 
-typedef const __attribute__((address_space(4))) uint32_t cu32;
 typedef const __attribute__((address_space(1))) uint8_t gu8;    // global memory, named for ld()
 typedef const __attribute__((address_space(1))) uint32_t gu32;
-typedef __attribute__((address_space(1))) uint8_t gw8;  // global memory, written
-typedef __attribute__((address_space(1))) int16_t g16;
-typedef __attribute__((address_space(1))) float gf32;
 
 // One segment: strip x0, rows [yb, ye). FAST: every staged search position lies inside the
 // image (one unaligned dword load per lane and row); otherwise replicate-clamped
@@ -440,8 +366,7 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
     //   segment start: the init forms the single-column sums as before; G3 is summed from them once, in place.
     //   box phase: v[k] = G3[k] + G3[k + 3] + G3[k + 6] (R = 4), G3[k] (R = 1): no running sum.
     // The clamped copy keeps the single-column form; a segment is wholly one or the other.
-    constexpr bool CG = kRowstepColgroup && MRG && SIDE == 0 && NW == 1 && (R == 4 || R == 1) && kRowstepKey2 &&
-                        !kRowstepPairtail && kRowstepOverlap && kRowstepAhead && !kRowstepSref;
+    constexpr bool CG = kRowstepColgroup && MRG && SIDE == 0 && NW == 1 && (R == 4 || R == 1) && kRowstepKey2;
     constexpr int NCU = CG ? G::NG3 : NC;  // columns (groups) of the rotated loop's column update
     const bool m_s = tid < NJ4;
     const int m_r = CG ? max(NC4 - 1 - (tid - NJ4), 0) : min(tid - NJ4, NC4 - 1);  // reference dword of a non-search lane
@@ -466,13 +391,6 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
             *reinterpret_cast<uint4 *>(sp) = make_uint4(__builtin_amdgcn_perm(nb, w, m_sel0), __builtin_amdgcn_perm(nb, w, m_sel1),
                                                         __builtin_amdgcn_perm(nb, w, m_sel2), __builtin_amdgcn_perm(nb, w, m_sel3));
     };
-    // SR0 (the builds that batch their init rows, IBT below, and stage merged rows): step yb's prefetch - rows
-    // yb + 1 + R and yb - R, the one an init row again - issued once the init batch is in LDS, in front of the init SAD
-    // loop, and held in sr_n / sr_o across it.  Issued at the top of step yb, whose body is only the box phase, the
-    // staging of that step waits for a whole global round trip.  Only the loads move: the init's LDS rows overlap the
-    // slots, so the stores to the slots stay behind the barrier that ends the init.
-    constexpr bool SR0 = kSegstartRow0 && kSegstartBatch && MRG && R <= 4 && (SIDE == 0 || SIDE == 4);
-    uint32_t sr_n = 0, sr_o = 0;
     auto ld = [&](int r, uint32_t &w0, uint32_t &w1, uint32_t &w2, uint32_t &w3, uint32_t &rf) __attribute__((always_inline)) {
         const int yy = clampi2(r, 0, H - 1);
         // The row base is wave-uniform and the lane's part a small non-negative offset (FAST:
@@ -771,12 +689,6 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
             }
         }
         block_sync<NW>();
-        if constexpr (SR0) {
-            static_assert(!SR0 || IBT, "the first step's rows ride behind the batched init loads");
-            ldm(yb + 1 + R, sr_n);
-            ldm(yb - R, sr_o);
-            __builtin_amdgcn_sched_barrier(0);
-        }
         // this lane's pair entry for column c: TP_g[d0 + NC - 1 - c] (8-B aligned); groups in a
         // runtime loop, columns unrolled (a full unroll of both hoists every LDS read and spills)
         const uint8_t *tb = smem + d0 * 8;
@@ -785,7 +697,7 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
 #pragma unroll
         for (int c = 0; c < NC; ++c) ae[c] = ao[c] = 0;
         // IAH: chunk q + 1's reads (4 pair entries and the broadcast reference dwords) issued in front of chunk q's
-        // SADs, two register sets pinned with sched_barrier(0) as AHD does in the row loop: only a group's first
+        // SADs, two register sets pinned with sched_barrier(0) as in the rotated row loop: only a group's first
         // chunk waits with a full drain.  Left to the scheduler, every read sits directly in front of its use
         // (18 drains per group at R = 4, the wave idle on LDS latency).
         // The R >= 6 builds (88 and more accumulators) gain scratch with it and keep the one-set loop.
@@ -941,76 +853,31 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
 
     // RL2: the lane's bytes in slot par ^ 2 of the first step
     uint32_t stg = (MRG ? m_lane : (uint32_t)(16 * tid)) + (uint32_t)((2 - (yb & 1) * 2) * SLOT);
-    // DIVQ: the left tail's sub-pixel quotient by subpix_quot (dsx_subpix.h) instead of div_trunc_small and its
-    // two divergent fix-up branches.
-    // PTAIL (pair layout, one-wave left pass; off by default, see DSX_ROWSTEP_PAIRTAIL): the epilogue's tail -
-    // valid band, sub-pixel step, output formation, the two global stores - serves one pixel per lane pair, so
-    // half of its issue slots repeat the other half.  With PTAIL it runs once per two rows, on 64 (row, pixel)
-    // outputs: the first row of a pair keeps its scan results in kp0 / kp1 across the next step.
-    constexpr bool PTAIL = kRowstepPairtail && !SSD && SIDE == 0 && NW == 1;
-    constexpr bool DIVQ = kRowstepDivq && !SSD && SIDE == 0;
-    uint32_t kp0 = 0, kp1 = 0;
+    // DIVQ (pair layout, left pass): the tail's sub-pixel quotient by subpix_quot (dsx_subpix.h); the other tails keep
+    // div_trunc_small and its two divergent fix-up branches.
+    constexpr bool DIVQ = !SSD && SIDE == 0;
     // OVL (pair layout, one-wave left pass, key argmin: R <= 5): the row loop rotated by half a step.  The
     // epilogue of row y - 1 reads only the tile, the column update of row y only the staged slots and the
     // column sums, and the tile is not rewritten before row y's box phase, so step y runs the two together:
     // the epilogue is cut into stages at its dependent LDS reads (the eight block reads, the winning block, the
     // two neighbour costs, the sub-pixel step) and stage s is issued in front of column chunk s, with one chunk
     // of SADs between a read and its first use.  sched_barrier(0) pins the pieces in source order.  The stages
-    // are branch-free (the neighbour costs are read for every pixel, as in PTAIL, and dropped where no step
-    // applies); the wave-uniform uniqueness and parabola-float branches and the stores follow the last chunk.
+    // are branch-free (the neighbour costs are read for every pixel and dropped where no step applies); the
+    // wave-uniform uniqueness and parabola-float branches follow the last chunk.
     // A segment's first step has no epilogue and one epilogue drains the segment behind its last step.
-    // AHD: chunk q + 1's LDS reads issued in front of chunk q's SADs, two register sets (only a step's first
-    // chunk waits).  Both forms take the column update in 4-column chunks, two sets of which hold what one
-    // 8-column chunk does.
-    constexpr bool CUQ = !SSD && SIDE == 0 && NW == 1 && R < 6 && kRowstepKey2 && !PTAIL;
-    constexpr bool OVL = kRowstepOverlap && CUQ, AHD = kRowstepAhead && CUQ;
-    // STA (the loops that run OVL): rotated, the step holds row y - 1's two output stores behind its last chunk, so
-    // staging behind the box phase waits with vmcnt(1) / vmcnt(0) behind them - vmcnt counts loads and stores in
-    // order, so that is a store round trip per step.  The staging of step y + 1's rows therefore stands directly
-    // behind the last chunk, in front of the stages that store: slots par ^ 2 and (par ^ 2) + 1 were last read by
-    // step y - 1's column update, and a one-wave block's LDS operations execute in order.  A segment's first step
-    // has no column update and no store in front of its staging, which stays behind the box phase.
-    constexpr bool STA = kRowstepStageahead && OVL;
-    // STL (the same loops): the loads keep the whole step to land - the staging stays behind the box phase - and the
-    // two output stores of row y - 1 follow it: the outputs (the x16 value, the parabola float) are held across the
-    // box phase in e_fx / e_pf, and the next wait that counts the stores is the next step's staging, a step later.
-    constexpr bool STL = kRowstepStorelate && OVL;
+    // The column update runs in 4-column chunks with chunk q + 1's LDS reads issued in front of chunk q's SADs, in
+    // two register sets (only a step's first chunk waits), which together hold what one 8-column chunk does.
+    // The two output stores of row y - 1 stand at the end of step y, behind the staging of step y + 1's rows: behind
+    // the last chunk they would be older than the staging's loads, and vmcnt counts loads and stores in order, so the
+    // staging would wait for a store round trip per step.  The outputs (the x16 value, the parabola float) are held
+    // across the box phase in e_fx / e_pf, and the next wait that counts the stores is the next step's staging.
+    constexpr bool OVL = !SSD && SIDE == 0 && NW == 1 && R < 6 && kRowstepKey2;
     int e_fx = 0;
     float e_pf = 0.0f;
-    static_assert(!CG || (CUQ && OVL && AHD), "group sums: the rotated loop with its reads ahead");
+    static_assert(!CG || OVL, "group sums: the rotated loop");
     constexpr int CQ = 4, NQ = (NCU + CQ - 1) / CQ;
-    // SREF (the unaligned-dword copy of these loops): the reference row is wave-uniform, so the column update takes
-    // it from SGPRs - v_sad_u8 / v_sad_hi_u8 are VOP3 and read the reference byte as their one scalar operand -
-    // instead of 2 * NC4 broadcast ds_read_b128 per step.  A row is bytes [x0 - R, x0 - R + 4 NC4) of the reference
-    // image, inside the row by the segment's FAST test; the pointer has any alignment, so a step reads the aligned
-    // dwords that hold one of those bytes (NC4, + 1 when misaligned: the last offset below repeats dword NC4 - 1 when
-    // aligned, never a dword past the row's last needed byte), and chunk q takes its dword with one s_lshr_b64 of
-    // dwords q, q + 1 and each column's byte with one s_and / s_bfe / s_lshr.  Scalar memory returns out of order
-    // with LDS operations, so its consumer waits with lgkmcnt(0): the two rows of step y + 1 are loaded in one batch
-    // behind step y's last chunk, where step y's dwords are dead, and first used by chunk 0 of step y + 1, the one
-    // chunk that waits for its LDS reads anyway.  Read only; the clamped copy and the init keep the LDS form.
-    // R = 5 (12 dwords per row) keeps the LDS form: with SREF its kernel spills 8 B to scratch at the segment starts.
-    constexpr bool SREF = kRowstepSref && CUQ && FAST && OVL && R < 5;
-    // SRA: both copies of such a loop re-read the launch arguments of the stages behind the chunks (ea in estage)
-    constexpr bool SRA = kRowstepSargs && CUQ && OVL && R < 5;
-    static_assert(!SREF || NQ == NC4, "one reference dword per column chunk");
-    uint32_t qn[NC4 + 1] = {}, qo[NC4 + 1] = {}, shn = 0, sho = 0;
-    auto sld = [&](int r, uint32_t(&q)[NC4 + 1], uint32_t &sh) __attribute__((always_inline)) {
-        const int yy = clampi2(r, 0, H - 1);
-        const uintptr_t p = (uintptr_t)(a.ref + fin + (long)yy * stride + (x0 - R));
-        typedef const __attribute__((address_space(4))) uint8_t cu8;
-        cu8 *b = (cu8 *)(p & ~(uintptr_t)3);
-#pragma unroll
-        for (int i = 0; i < NC4; ++i) q[i] = *(cu32 *)(b + 4 * i);
-        q[NC4] = *(cu32 *)(b + ((((uint32_t)p + 4u * NC4 - 1u) & ~3u) - ((uint32_t)p & ~3u)));
-        sh = ((uint32_t)p & 3u) * 8u;
-    };
-    // column c0 + c's reference byte of a row's dword (its misalignment shifted out)
-    auto sbyte = [](uint32_t w, int c) __attribute__((always_inline)) -> uint32_t {
-        return c == 3 ? w >> 24 : (w >> (8 * c)) & 0xFFu;
-    };
     // Tile reads per stage and read stages: one read (4 VGPRs in flight) where the chunks suffice, two otherwise.
-    // With two, R = 4 and R = 5 spilled 8 B with both forms on; four overran the 168 VGPRs with OVL alone.
+    // With two, R = 4 and R = 5 spilled 8 B; four overran the 168 VGPRs even without the reads ahead.
     // Stages 0 .. NRS - 1 read, NRS block keys, NRS + 1 element keys, NRS + 2 sub-pixel step, NRS + 3 outputs.
     constexpr int RPS = NQ >= 10 ? 1 : 2, NRS = 8 / RPS;
     static_assert(NQ >= NRS + 2, "a column chunk per stage up to the element keys");
@@ -1025,9 +892,9 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
                                                    __builtin_elementwise_min(as2(v.z), as2(v.w)));
         return umin2(mm.x, mm.y);
     };
-    // rl / er: the sub-pixel and output stages read their launch arguments from er (SRA: the row loop's re-read ones
-    // behind its last chunk) instead of the segment's
-    // the two output stores of a row, apart from the stage that forms the outputs where that stage defers them (STL)
+    // the two output stores of a row, apart from the stage that forms the outputs where that stage defers them
+    // ea: the row loop's own copy of the launch arguments.  Taken from the segment's copy (a) the same values come
+    // out as another instruction stream (tools/isa_same.py: bm2<R, SAD, 1, 0>, R <= 5).
     auto estore = [&](int ey, const Bm2Args &ea) __attribute__((always_inline)) {
         if (eh == 0 && ex < W) {
             const long o = fout + (long)ey * W + ex;
@@ -1035,16 +902,10 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
             if (ea.out_float) ea.out_float[o] = ea.float_mode == 0 ? (float)(int16_t)e_fx * 0.0625f : e_pf;
         }
     };
-    // dfr: the output stage leaves its stores to estore
-    auto estage = [&](auto sc, int ey, auto rl, const Bm2Args &er, auto dfr) __attribute__((always_inline)) {
+    // dfr: the output stage leaves its stores to estore (the row loop; the drain behind a segment stores at once)
+    auto estage = [&](auto sc, int ey, auto dfr) __attribute__((always_inline)) {
         constexpr int s = decltype(sc)::value;
-        constexpr bool RL = decltype(rl)::value;
         constexpr bool DFR = decltype(dfr)::value;
-        auto pick = [&]() __attribute__((always_inline)) -> const Bm2Args & {
-            if constexpr (RL) return er;
-            else return a;
-        };
-        const Bm2Args &ea = pick();
         static_assert(!OVL || (NB == 8 && TPP == 2), "overlapped epilogue: 64 disparities per lane, two lanes per pixel");
         constexpr int GB = Dp / 8 <= 16 ? 4 : (Dp / 8 <= 32 ? 5 : 6);
         if constexpr (s <= NRS) {  // RPS block reads per stage; the block keys (KEY2 of the sequential form) of those before
@@ -1075,16 +936,15 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
             ecm = pc[-1];
             ecp = pc[1];
         } else if constexpr (s == NRS + 2) {  // sub-pixel step
-            esp = ea.subpix && eb > 0 && eb < D - 1;
+            esp = a.subpix && eb > 0 && eb < D - 1;
             int32_t den = (int32_t)ecm + (int32_t)ecp - 2 * (int32_t)ecb;
             eden = den < 1 ? 1 : den;
             const int32_t num = ((int32_t)ecm - (int32_t)ecp) * 16 + eden;
-            const int32_t q = DIVQ ? subpix_quot(num, 2 * eden) : div_trunc_small(num, 2 * eden);
+            const int32_t q = subpix_quot(num, 2 * eden);  // for every pixel: the stage stays branch-free
             ef = eb * 16 + (esp ? q : 0);
         } else {  // uniqueness, outputs
-            const uint32_t padv_e = RL ? er.padv : padv;
             bool valid = ex < W && ex >= m + D - 1 && ex <= W - 1 + m;
-            if (ea.uniq > 0) {
+            if (a.uniq > 0) {
                 const int rel = eb - eh * DSL;
                 uint32_t nm = 0xFFFFFFFFu;
 #pragma unroll
@@ -1109,12 +969,12 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
                     }
                 }
                 nm = gmin<TPP>(nm);
-                const uint32_t real_max = padv_e < (1u << 24) ? padv_e : (1u << 24);
-                if (nm < real_max && nm * (uint32_t)(100 - ea.uniq) < ecb * 100u) valid = false;
+                const uint32_t real_max = padv < (1u << 24) ? padv : (1u << 24);
+                if (nm < real_max && nm * (uint32_t)(100 - a.uniq) < ecb * 100u) valid = false;
             }
             if constexpr (DFR) {
                 e_fx = valid ? (int16_t)(m * 16 + ef) : (int16_t)((m - 1) * 16);
-                if (eh == 0 && ex < W && ea.out_float && ea.float_mode != 0) {
+                if (eh == 0 && ex < W && a.out_float && a.float_mode != 0) {
                     float pf = (float)(m + eb);
                     if (esp) pf = (float)(m + eb) + (float)((int32_t)ecm - (int32_t)ecp) / (float)(2 * eden);
                     e_pf = valid ? pf : (float)(m - 1);
@@ -1122,30 +982,19 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
             } else if (eh == 0 && ex < W) {
                 const long o = fout + (long)ey * W + ex;
                 const int16_t fx = valid ? (int16_t)(m * 16 + ef) : (int16_t)((m - 1) * 16);
-                if (ea.out_fixed) ea.out_fixed[o] = fx;
-                if (ea.out_float) {
-                    if (ea.float_mode == 0) {
-                        ea.out_float[o] = (float)fx * 0.0625f;
+                if (a.out_fixed) a.out_fixed[o] = fx;
+                if (a.out_float) {
+                    if (a.float_mode == 0) {
+                        a.out_float[o] = (float)fx * 0.0625f;
                     } else {
                         float pf = (float)(m + eb);
                         if (esp) pf = (float)(m + eb) + (float)((int32_t)ecm - (int32_t)ecp) / (float)(2 * eden);
-                        ea.out_float[o] = valid ? pf : (float)(m - 1);
+                        a.out_float[o] = valid ? pf : (float)(m - 1);
                     }
                 }
             }
         }
     };
-    if constexpr (SREF) {  // the rows of the segment's first column update (step yb + 1)
-        sld(yb + 1 + R, qn, shn);
-        sld(yb - R, qo, sho);
-    }
-    if constexpr (SR0) {  // step yb's staging: the init's rows are consumed (the barrier that ends the init) and the loads old
-        if (yb + 1 < ye) {
-            stm(smem + stg, sr_n);
-            stm(smem + stg + SLOT, sr_o);
-        }
-        stg = (2 * m_lane + (uint32_t)(2 * SLOT)) - stg;
-    }
     for (int y = yb; y < ye; ++y) {
         const Bm2Args &a = kargs_row<SIDE == 3>(a_in);
 #ifdef DSX_STAMPS
@@ -1183,12 +1032,7 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
         // are dead.  First form (!RL2): under `if (more)`; writing the zeros then waits for the
         // previous step's loads and stores (s_waitcnt vmcnt(0) at the loop header).
         uint32_t pn0 = 0, pn1 = 0, pn2 = 0, pn3 = 0, pnr = 0, po0 = 0, po1 = 0, po2 = 0, po3 = 0, por = 0;
-        if constexpr (SR0) {  // step yb's rows were loaded in front of the init SAD loop and staged in front of this loop
-            if (y > yb) {
-                ldm(y + 1 + R, pn0);
-                ldm(y - R, po0);
-            }
-        } else if constexpr (MRG) {
+        if constexpr (MRG) {
             ldm(y + 1 + R, pn0);
             ldm(y - R, po0);
         } else if (RL2 || more) {
@@ -1219,22 +1063,20 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
                 }
             }
           }
-        } else if constexpr (OVL || AHD) {
+        } else if constexpr (OVL) {
           if (y > yb) {
             // this lane's staged words of chunk q (columns [CQ q, CQ q + CQ)), both slots: s_chunk / ref_chunk
-            // of the left form at the chunk width of this path
+            // of the left form at the chunk width of this path, in register set q & 1
             uint32_t sn[2][CQ + 1], so[2][CQ + 1], rn[2][CQ], ro[2][CQ];
             uint32_t nxn = 0, nxo = 0;
             auto rd = [&](auto qc) __attribute__((always_inline)) {
-                constexpr int q = decltype(qc)::value, c0 = CQ * q, t = AHD ? (q & 1) : 0;
+                constexpr int q = decltype(qc)::value, c0 = CQ * q, t = q & 1;
                 const uint8_t *bn = (const uint8_t *)__builtin_assume_aligned(smem + par * SLOT + d0 * 4, 8);
                 const uint8_t *bo = (const uint8_t *)__builtin_assume_aligned(smem + (par + 1) * SLOT + d0 * 4, 8);
-                if constexpr (!SREF) {
-                    const uint4 vn = *reinterpret_cast<const uint4 *>(smem + par * SLOT + G::SROW + 4 * c0);
-                    const uint4 vo = *reinterpret_cast<const uint4 *>(smem + (par + 1) * SLOT + G::SROW + 4 * c0);
-                    rn[t][0] = vn.x; rn[t][1] = vn.y; rn[t][2] = vn.z; rn[t][3] = vn.w;
-                    ro[t][0] = vo.x; ro[t][1] = vo.y; ro[t][2] = vo.z; ro[t][3] = vo.w;
-                }
+                const uint4 vn = *reinterpret_cast<const uint4 *>(smem + par * SLOT + G::SROW + 4 * c0);
+                const uint4 vo = *reinterpret_cast<const uint4 *>(smem + (par + 1) * SLOT + G::SROW + 4 * c0);
+                rn[t][0] = vn.x; rn[t][1] = vn.y; rn[t][2] = vn.z; rn[t][3] = vn.w;
+                ro[t][0] = vo.x; ro[t][1] = vo.y; ro[t][2] = vo.z; ro[t][3] = vo.w;
                 sn[t][0] = c0 == 0 ? *reinterpret_cast<const uint32_t *>(bn + NC * 4) : nxn;
                 so[t][0] = c0 == 0 ? *reinterpret_cast<const uint32_t *>(bo + NC * 4) : nxo;
 #pragma unroll
@@ -1248,46 +1090,34 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
                 }
             };
             auto sads = [&](auto qc) __attribute__((always_inline)) {
-                constexpr int q = decltype(qc)::value, c0 = CQ * q, t = AHD ? (q & 1) : 0;
-                // SREF: the chunk's reference dword of either row, on the scalar unit
-                uint32_t wn = 0, wo = 0;
-                if constexpr (SREF) {
-                    // the upper dword passes through an empty asm (in place, no instruction): left free, the two
-                    // array elements are combined into one 64-bit access, which keeps the arrays out of registers
-                    uint32_t hn = qn[q + 1], ho = qo[q + 1];
-                    asm("" : "+s"(hn));
-                    asm("" : "+s"(ho));
-                    wn = (uint32_t)((((uint64_t)hn << 32) | qn[q]) >> shn);
-                    wo = (uint32_t)((((uint64_t)ho << 32) | qo[q]) >> sho);
-                }
+                constexpr int q = decltype(qc)::value, c0 = CQ * q, t = q & 1;
 #pragma unroll
                 for (int c = 0; c < CQ; ++c) {
                     if (c0 + c < NCU) {
-                        const uint32_t bn = SREF ? sbyte(wn, c) : rn[t][c], bo = SREF ? sbyte(wo, c) : ro[t][c];
+                        const uint32_t bn = rn[t][c], bo = ro[t][c];
                         const uint32_t en = sad_hi_u8(bn, sn[t][c], __builtin_amdgcn_sad_u8(bn, sn[t][c + 1], as1(cs[c0 + c])));
                         const uint32_t lo = sad_hi_u8(bo, so[t][c], __builtin_amdgcn_sad_u8(bo, so[t][c + 1], 0u));
                         // pinned to this chunk (in place, no instruction): left free, the SADs - pure values whose
                         // next use is the box phase - are sunk behind the epilogue's branches, every staged
                         // word of the step is then held across it, and the loop spills
                         uint32_t v = en - lo;
-                        if constexpr (OVL) asm volatile("" : "+v"(v));
+                        asm volatile("" : "+v"(v));
                         cs[c0 + c] = as2(v);
                     }
                 }
             };
-            // epilogue stage q in front of chunk q
+            // epilogue stage q and chunk q + 1's reads in front of chunk q
             auto chunk = [&](auto qc) __attribute__((always_inline)) {
                 constexpr int q = decltype(qc)::value;
                 if constexpr (q < NQ) {
                     __builtin_amdgcn_sched_barrier(0);
-                    if constexpr (OVL && q < NRS + 3) estage(qc, y - 1, std::false_type{}, a, std::false_type{});
-                    if constexpr (!AHD) rd(qc);
-                    else if constexpr (q + 1 < NQ) rd(std::integral_constant<int, q + 1>{});
+                    if constexpr (q < NRS + 3) estage(qc, y - 1, std::false_type{});
+                    if constexpr (q + 1 < NQ) rd(std::integral_constant<int, q + 1>{});
                     __builtin_amdgcn_sched_barrier(0);
                     sads(qc);
                 }
             };
-            if constexpr (AHD) rd(std::integral_constant<int, 0>{});
+            rd(std::integral_constant<int, 0>{});
             chunk(std::integral_constant<int, 0>{}); chunk(std::integral_constant<int, 1>{});
             chunk(std::integral_constant<int, 2>{}); chunk(std::integral_constant<int, 3>{});
             chunk(std::integral_constant<int, 4>{}); chunk(std::integral_constant<int, 5>{});
@@ -1296,34 +1126,9 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
             chunk(std::integral_constant<int, 10>{}); chunk(std::integral_constant<int, 11>{});
             static_assert(NQ <= 12 && NQ >= 7, "chunks of the overlapped column update");
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (STA) {  // step y + 1's rows to their slots, in front of the tail's stores
-                if constexpr (MRG) {
-                    if (more) {
-                        stm(smem + stg, pn0);
-                        stm(smem + stg + SLOT, po0);
-                    }
-                    stg = (2 * m_lane + (uint32_t)(2 * SLOT)) - stg;
-                } else {
-                    if (more) {
-                        st_at(smem + stg, pn0, pn1, pn2, pn3, pnr);
-                        st_at(smem + stg + SLOT, po0, po1, po2, po3, por);
-                    }
-                    stg = (uint32_t)(32 * tid + 2 * SLOT) - stg;
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            if constexpr (SREF) {  // step y + 1's rows (clamped like the prefetch: the segment's last step reads a row nobody uses)
-                sld(y + 1 + R, qn, shn);
-                sld(y - R, qo, sho);
-            }
-            // SREF: the stages behind the chunks re-read their launch arguments in the same batch (kargs_row), like the
-            // LR pass's row loop: held across the loop next to the reference dwords they spill to VGPR lanes
-            const Bm2Args &ea = kargs_row<SRA>(a);
-            if constexpr (SRA) __builtin_amdgcn_sched_barrier(0);
-            if constexpr (OVL) {
-                if constexpr (NQ < NRS + 3) estage(std::integral_constant<int, NRS + 2>{}, y - 1, std::integral_constant<bool, SRA>{}, ea, std::false_type{});
-                estage(std::integral_constant<int, NRS + 3>{}, y - 1, std::integral_constant<bool, SRA>{}, ea, std::integral_constant<bool, STL>{});
-            }
+            // the stages no chunk was left for; the outputs are formed here and stored at the end of the step
+            if constexpr (NQ < NRS + 3) estage(std::integral_constant<int, NRS + 2>{}, y - 1, std::false_type{});
+            estage(std::integral_constant<int, NRS + 3>{}, y - 1, std::true_type{});
           }
         } else if (y > yb) {
             uint32_t nxn = 0, nxo = 0;
@@ -1558,33 +1363,29 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
         // block has passed the mid-step barrier above since then, and the barrier that ends the
         // step orders these writes before step y + 1 reads them (the end barrier of step y - 1 alone
         // already separates them from their last readers).  The epilogue reads the tile only.
-        // That holds for the sequential loops.  Rotated (OVL), the step's stores are those of row y - 1's tail and
-        // stand behind the last chunk, in front of this place: the waits below drain them again unless the staging
-        // moves in front of them (STA) or they move behind it (STL).
+        // That holds for the sequential loops.  Rotated (OVL), the step's stores are those of row y - 1's tail, whose
+        // outputs were formed behind the last chunk: they follow the staging (estore below).
         if constexpr (RL2) {
             // the lane's staging address alternates between slots 0 and 2: carried across the steps and
             // flipped with one subtraction (rebuilt from par, it came out as one v_mad per store)
-            // STA: only the segment's first step stages here (the others did behind their last chunk); SR0: every
-            // step but the first, whose rows were staged in front of the loop
-            [[maybe_unused]] const bool late = STA ? (!SR0 && y == yb) : (!SR0 || y > yb);
             if constexpr (MRG) {
-                if (more && late) {
+                if (more) {
                     stm(smem + stg, pn0);
                     stm(smem + stg + SLOT, po0);
                 }
-                if (late) stg = (2 * m_lane + (uint32_t)(2 * SLOT)) - stg;
+                stg = (2 * m_lane + (uint32_t)(2 * SLOT)) - stg;
             } else if constexpr (SIDE != 3) {
-                if (more && late) {
+                if (more) {
                     st_at(smem + stg, pn0, pn1, pn2, pn3, pnr);
                     st_at(smem + stg + SLOT, po0, po1, po2, po3, por);
                 }
-                if (late) stg = (uint32_t)(32 * tid + 2 * SLOT) - stg;
+                stg = (uint32_t)(32 * tid + 2 * SLOT) - stg;
             } else if (more) {  // LR pass, at its register budget: no carried address (R = 1 spilled 16 B more)
                 st(par ^ 2, pn0, pn1, pn2, pn3, pnr);
                 st((par ^ 2) + 1, po0, po1, po2, po3, por);
             }
         }
-        if constexpr (STL) {  // row y - 1's outputs, formed behind the last chunk
+        if constexpr (OVL) {  // row y - 1's outputs, formed behind the last chunk
             if (y > yb) estore(y - 1, a);
         }
         DSX_STAMP(5);
@@ -1758,62 +1559,6 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
                     const uint32_t real_max = padv < (1u << 24) ? padv : (1u << 24);
                     if (nm < real_max && nm * (uint32_t)(100 - a.uniq) < cb * 100u) valid = false;
                 }
-                if constexpr (PTAIL) {
-                    // Scan part, every row: what the tail needs of this row is (b, cb, valid, cm, cp), the same
-                    // in both lanes of the pixel, packed into two VGPRs.  The neighbour costs are read
-                    // unconditionally (b - 1 >= -1 and b + 1 <= Dp stay inside the block's LDS: the slot bytes
-                    // before the tile, the row's padding); the tail drops them where no sub-pixel step applies.
-                    const uint16_t *pc = reinterpret_cast<const uint16_t *>(tile + k * PITCH) + b;
-                    u16x2 mp;
-                    mp.x = pc[-1];
-                    mp.y = pc[1];
-                    const uint32_t c0 = (cb << 16) | ((uint32_t)valid << 15) | (uint32_t)b, c1 = as1(mp);
-                    // Tail part, once per two rows of the segment (paired by y - yb, so nothing is kept across
-                    // segments): on a pair's second row lane h = 0 finishes the kept row y - 1 and lane h = 1
-                    // row y; a segment's unpaired last row runs it on the h = 0 lanes alone.  Wave-uniform.
-                    int sec = (y - yb) & 1;
-                    asm("" : "+s"(sec));  // stays a scalar integer: left free it becomes a loop-carried lane mask
-                    const bool second = sec != 0;
-                    if (second || !more) {
-                        const bool prev = second && h == 0;
-                        const uint32_t s0 = prev ? kp0 : c0, s1 = prev ? kp1 : c1;
-                        const int tb = (int)(s0 & 0x7FFFu);
-                        const int32_t tcb = (int32_t)(s0 >> 16), cm = (int32_t)(s1 & 0xFFFFu), cp = (int32_t)(s1 >> 16);
-                        const bool tvalid = (s0 & 0x8000u) != 0;
-                        int32_t f = tb * 16;
-                        float pf = (float)(m + tb);
-                        if (a.subpix) {
-                            const bool sp = tb > 0 && tb < D - 1;
-                            int32_t den = cm + cp - 2 * tcb;
-                            den = den < 1 ? 1 : den;
-                            const int32_t num = (cm - cp) * 16 + den;
-                            const int32_t q = DIVQ ? subpix_quot(num, 2 * den) : div_trunc_small(num, 2 * den);
-                            f += sp ? q : 0;
-                            if (a.float_mode == 1 && sp) pf = (float)(m + tb) + (float)(cm - cp) / (float)(2 * den);
-                        }
-                        if ((second || h == 0) && x < W) {
-                            // one store writes two rows: the row base is wave-uniform (y - 1 on a second row,
-                            // pinned to SGPRs like the prefetch's row bases), the lane's part carries + W for h = 1
-                            long ro = fout + (long)(y - sec) * W;
-                            asm("" : "+s"(ro));
-                            const uint32_t xh = (uint32_t)(x + (h ? W : 0));
-                            const int16_t fx = tvalid ? (int16_t)(m * 16 + f) : (int16_t)((m - 1) * 16);
-                            if (a.out_fixed) {
-                                int16_t *rowp = a.out_fixed + ro;
-                                asm("" : "+s"(rowp));
-                                *(g16 *)((gw8 *)rowp + 2u * xh) = fx;
-                            }
-                            if (a.out_float) {
-                                float *rowp = a.out_float + ro;
-                                asm("" : "+s"(rowp));
-                                *(gf32 *)((gw8 *)rowp + 4u * xh) = a.float_mode == 0 ? (float)fx * 0.0625f : (tvalid ? pf : (float)(m - 1));
-                            }
-                        }
-                    } else {
-                        kp0 = c0;
-                        kp1 = c1;
-                    }
-                } else {
                 int32_t f = b * 16;
                 float pf = (float)(m + b);
                 if (a.subpix && b > 0 && b < D - 1) {
@@ -1846,7 +1591,6 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
                     if (a.out_fixed) a.out_fixed[o] = fx;
                     if (a.out_float) a.out_float[o] = a.float_mode == 0 ? (float)fx * 0.0625f : (valid ? pf : (float)(m - 1));
                 }
-                }
             }
         }
         if (!RL2 && more) {  // first form: staged behind the epilogue
@@ -1859,7 +1603,7 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
     }
     if constexpr (OVL) {  // the segment's last row: nothing is kept across segments
         auto dr = [&](auto sc) __attribute__((always_inline)) {
-            if constexpr (decltype(sc)::value <= NRS + 3) estage(sc, ye - 1, std::false_type{}, a, std::false_type{});
+            if constexpr (decltype(sc)::value <= NRS + 3) estage(sc, ye - 1, std::false_type{});
         };
         dr(std::integral_constant<int, 0>{}); dr(std::integral_constant<int, 1>{}); dr(std::integral_constant<int, 2>{});
         dr(std::integral_constant<int, 3>{}); dr(std::integral_constant<int, 4>{}); dr(std::integral_constant<int, 5>{});
@@ -1884,17 +1628,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((SSD &&
     uint64_t t_prev = 0;
     uint64_t nsteps = 0;
 #endif
-    // SPART: the block's partition words through the scalar unit, issued here so that their latency lies under
-    // the fill and reset loops below (the table is written by the host before the launch: read-only here).  Up to
-    // R = 5: two R >= 6 builds at their register budget gain scratch with the two words held across those loops.
-    constexpr bool SPART = kSegstartSpart && R <= 5;
-    int sp0 = 0, sp1 = 0;
-    if constexpr (SPART) {
-        typedef const __attribute__((address_space(4))) int ci32;
-        ci32 *pp = (ci32 *)((uintptr_t)a.part + 4 * (uintptr_t)blockIdx.x);
-        sp0 = pp[0];
-        sp1 = pp[1];
-    }
 
     // ---- left pass: columns of strips that lie entirely in the invalid band ----
     if ((side == 0 || side == 3 || side == 4) && (a.out_fixed || a.out_float)) {
@@ -1929,7 +1662,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((SSD &&
 
     // ---- work partition (host-computed, bm2_partition): block b owns linear (frame, strip, row)
     // units [part[b], part[b+1]); nframes * H * W < 2^31 (host check)
-    const int lin0 = SPART ? sp0 : a.part[blockIdx.x], lin1 = SPART ? sp1 : a.part[blockIdx.x + 1];
+    const int lin0 = a.part[blockIdx.x], lin1 = a.part[blockIdx.x + 1];
     constexpr bool lr_on = SIDE == 3;  // left pass that also builds the right-view winners
     int qcur = -1;
     int pe[3];  // rows done at which the priority drops (progress bands pt1..pt3 of 256)

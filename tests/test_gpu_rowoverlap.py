@@ -1,7 +1,7 @@
 """Rotated row loop of the fused pass (csrc/dsx_bm.hip, pair layout, one-wave left pass, block sizes up to 11):
-step y of a segment runs the epilogue of row y - 1 between the chunks of row y's column update
-(-DDSX_ROWSTEP_OVERLAP), and the column update reads its staged words one chunk ahead (-DDSX_ROWSTEP_AHEAD).  The
-cases hold for every setting of the two switches.
+step y of a segment runs the epilogue of row y - 1 between the chunks of row y's column update, and the column
+update reads its staged words one chunk ahead.  Both are the only form in the source (their A/B switches were
+folded once settled); the cases guard the segment shapes below, at which the rotation can go wrong.
 
 A segment's first step has no epilogue and one epilogue drains the segment behind its last step, so what decides
 the code path is the segment length: 1 row is init + drain only, 2 rows have one overlapped step.  The cases are

@@ -1,13 +1,14 @@
 """Left tail of the fused pass (csrc/dsx_bm.hip, pair layout): its branch-free sub-pixel quotient
-(csrc/dsx_subpix.h, the default build) and the tail once per two rows (-DDSX_ROWSTEP_PAIRTAIL=1, off by
-default).  The cases hold for both builds and were run on both.
+(csrc/dsx_subpix.h), and segments of every short length.  The length cases were written for a tail that ran once
+per two rows, a form that was rejected and removed from the source; they were run on that build and
+on the shipped one, and hold for the shipped tail, which runs once per row.
 
-With the paired tail a row step's scan leaves (winner, its cost, valid bit, the two neighbour costs) in both
-lanes of a pixel; the first row of a pair keeps them across the next step, the second row's tail finishes both
-rows at once (lane h = 0 the kept row, h = 1 its own), and a segment's unpaired last row runs the tail on the
-h = 0 lanes alone.  Rows are paired by their offset in the segment, so what decides the form is the segment
+The paired tail left a row step's scan results (winner, its cost, valid bit, the two neighbour costs) in both
+lanes of a pixel; the first row of a pair kept them across the next step, the second row's tail finished both
+rows at once (lane h = 0 the kept row, h = 1 its own), and a segment's unpaired last row ran the tail on the
+h = 0 lanes alone.  Rows were paired by their offset in the segment, so what decided the form was the segment
 length: the cases below are chosen by it, from a restatement of the host partition (csrc/dsx_partition.h,
-equal block weights).  The quotient's cases are the tail classes (quotients 8, 0 and below 0, rows that take
+equal block weights), and guard a tail that holds anything across row steps.  The quotient's cases are the tail classes (quotients 8, 0 and below 0, rows that take
 no step) and disparity ranges of one, two and four waves per block.
 
 Every comparison is bit for bit over all pixels against the C oracle (oracle/cref.py): the int16 x16 map and

@@ -1,8 +1,9 @@
 """Segment start of the fused pass (csrc/dsx_bm.hip): the code between kernel entry and a segment's first row step -
-the block's partition words (-DDSX_SEGSTART_SPART), the loads of the 2R+1 init rows in one batch
-(-DDSX_SEGSTART_BATCH) and the init SAD loop's LDS reads one chunk ahead (-DDSX_SEGSTART_AHEAD).  The cases hold for
-every setting of the three switches; they were run on the builds AHEAD / BATCH / SPART = 1 1 0 (the default), 1 1 1,
-and, with the radius-4 unit (block 9) rebuilt, 1 0 0, 0 1 0 and 0 0 1.
+the block's partition words, the loads of the 2R+1 init rows in one batch (-DDSX_SEGSTART_BATCH) and the init SAD
+loop's LDS reads one chunk ahead (-DDSX_SEGSTART_AHEAD).  The cases hold for both settings of either switch; they
+were run on the default build and, with the radius-4 unit (block 9) rebuilt, on AHEAD / BATCH = 1 0 and 0 1, and also
+on builds that took the partition words through scalar loads at kernel entry, a form that was rejected and removed
+from the source.
 
 What these forms can get wrong is a row of the init (clamped into the frame at both ends, rows past 2R zero), the
 column chunk a read belongs to (the last one partial at odd radii), and the block's first and last unit.  So the

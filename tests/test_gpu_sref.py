@@ -1,9 +1,11 @@
-"""Reference row of the rotated row loop through the scalar unit (csrc/dsx_bm.hip, -DDSX_ROWSTEP_SREF; pair
-layout, one-wave left pass, block sizes up to 11, the strips that load unaligned dwords - "FAST" below).  A step
-reads the aligned dwords that hold the bytes [x0 - R, x0 - R + 4 NC4) of the entering and the leaving reference
-row and shifts the misalignment out, so what the change can get wrong is the alignment of the row pointer (base
-pointer, byte offset of a view, row stride), the last dword of a row, the rows taken before a segment's first
-step and behind its last one, and the byte of a column.  The cases hold with the switch on and off.
+"""Reference row of the rotated row loop (csrc/dsx_bm.hip; pair layout, one-wave left pass, block sizes up to
+11, the strips that load unaligned dwords - "FAST" below).  The cases were written for a form that took the row
+through the scalar unit (rejected and removed from the source): a step read the aligned dwords that
+hold the bytes [x0 - R, x0 - R + 4 NC4) of the entering and the leaving reference row and shifted the
+misalignment out.  The shipped loop reads the row from its staged LDS copy, and the cases guard what any form of
+that read can get wrong: the alignment of the row pointer (base pointer, byte offset of a view, row stride), the
+last dword of a row, the rows taken before a segment's first step and behind its last one, and the byte of a
+column.
 
 Every comparison is bit for bit over all pixels against the C oracle (oracle/cref.py): the int16 x16 map and
 the float map - float mode 'fixed' against x16 / 16 (exact in f32), 'parabola' by bit pattern.  Every case

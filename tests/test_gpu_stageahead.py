@@ -1,21 +1,15 @@
-"""Row staging and output stores of the rotated row loop of the fused pass (csrc/dsx_bm.hip, bm2_segment).  Three
-forms reorder them, each behind its own switch:
+"""Row staging and output stores of the rotated row loop of the fused pass (csrc/dsx_bm.hip, bm2_segment).  In the
+shipped form row y - 1's two output stores, formed behind step y's last column chunk, are issued at the end of step
+y, behind the staging of step y + 1's rows, which stands behind the box phase.  Two other orders were measured and
+rejected and are no longer in the source: the staging directly behind the last column chunk, in front of
+those stores, and a segment's first step's two rows loaded in front of the init SAD loop and staged in front of the row
+loop.  The cases were run on builds of all three forms and of their combinations; they hold for the shipped one and
+guard the shapes at which any such order can go wrong.
 
-  -DDSX_ROWSTEP_STORELATE (default 1): row y - 1's two output stores, formed behind step y's last column chunk, are
-      issued at the end of step y, behind the staging of step y + 1's rows;
-  -DDSX_ROWSTEP_STAGEAHEAD (default 0): step y writes the rows of step y + 1 to their LDS slots directly behind its
-      last column chunk, in front of those stores; a segment's first step has no column update and keeps its staging
-      behind the box phase;
-  -DDSX_SEGSTART_ROW0 (default 0): a segment's first step's two rows are loaded in front of the init SAD loop and
-      staged in front of the row loop.
-
-The cases hold for every setting of the three.  They were run on the builds STORELATE / STAGEAHEAD / ROW0 = 1 0 0 (the
-default), 0 1 0, 0 0 1, 0 1 1 and 1 0 1.
-
-What these forms can get wrong is which slot pair a step writes (it alternates on y & 1 and the carried staging
-address flips in a new place), a slot written while its last reader still needs it, an output stored for the wrong
+What it can get wrong is which slot pair a step writes (it alternates on y & 1 and the carried staging address
+flips once per step), a slot written while its last reader still needs it, an output stored for the wrong
 row or held across a step that has none, and the places the staging stands in: a one-step segment stages nothing
-that is used, a two-step segment uses the early-staged slots exactly once, and from three steps on a step reads what
+that is used, a two-step segment uses the first staged slots exactly once, and from three steps on a step reads what
 the step before staged.  So the cases are chosen by segment length, first-row parity and position
 in the frame, from a restatement of the host partition (csrc/dsx_partition.h, equal block weights) and of the
 kernel's test for the unaligned-dword copy ("f:" below; the others, "c:", take clamped bytes), and every case asserts
