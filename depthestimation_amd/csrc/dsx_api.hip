@@ -11,6 +11,7 @@
 
 #include "../../include/dsx.h"
 #include "dsx_internal.h"
+#include "dsx_partition.h"
 #include "dsx_plan.h"
 
 extern char **environ;  // the DSX_* tuning variables: dsx_env()
@@ -389,6 +390,13 @@ DsxEnv dsx_env() {
     return e;
 }
 
+// the strips a fused launch covers (bm2_strips, dsx_partition.h): all of them, or those meeting the valid band
+void set_strips(dsx::Bm2Args &a, const dsx_handle *h, bool band_only) {
+    const dsx::Bm2Strips s = dsx::bm2_strips(a.W, h->p.min_disp, h->p.num_disp, band_only, dsx::kStripWidth);
+    a.strip_begin = s.begin;
+    a.strip_count = s.count;
+}
+
 dsx::Bm2Args base_args(dsx_handle *h, int H, int W, int64_t stride, const DsxEnv &env = dsx_env()) {
     dsx::Bm2Args a{};
     a.stride = stride;
@@ -401,8 +409,7 @@ dsx::Bm2Args base_args(dsx_handle *h, int H, int W, int64_t stride, const DsxEnv
     a.subpix = h->p.subpixel;
     a.float_mode = h->p.float_mode;
     a.padv = pad_value(h, h->g.DB);
-    a.strip_begin = 0;
-    a.strip_count = (W + dsx::kStripWidth - 1) / dsx::kStripWidth;
+    set_strips(a, h, false);
     a.grid_override = h->p.grid_blocks;
     {
         // Balance (measured on C2-C5, profiles/README.md r01d): co-resident waves drop their issue
@@ -601,15 +608,7 @@ int run_fused(const Call &c) {
         // every strip: a right pixel's diagonal starts left of the valid band
         a.side = dsx::SIDE_LEFT_LR;
     } else {
-        // only strips meeting the valid band [m + D - 1, W - 1 + m] need a search
-        // (stereo_core.py:168 crops the rest; OpenCV's band lies inside it)
-        const int xlo = std::max(0, h->p.min_disp + h->p.num_disp - 1);
-        const int xhi = std::min(W - 1, W - 1 + h->p.min_disp);
-        a.strip_count = 0;
-        if (xlo <= xhi) {
-            a.strip_begin = xlo / dsx::kStripWidth;
-            a.strip_count = xhi / dsx::kStripWidth + 1 - a.strip_begin;
-        }
+        set_strips(a, h, true);  // only strips meeting the valid band need a search
     }
     uint64_t *tl = nullptr;
     const char *tlpath = env.timeline;

@@ -1682,6 +1682,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((SSD &&
         const int done0 = it - lin0;
         it += ye - yb;
         const int x0 = s * TX;
+        // bm2_fast (dsx_partition.h) is this expression; a call to it compiles to other code, so it is written out
         const int PB = side == 1 ? (x0 - R + m) : (x0 - R - m + NC - 1);
         const int NJ4 = (NJ + 3) / 4;
         const bool fast = (side == 1 ? (PB >= 0 && PB + 4 * NJ4 <= W - 1) : (PB - 4 * NJ4 >= 0 && PB <= W - 1)) &&
@@ -1798,76 +1799,36 @@ static hipError_t launch_bm2_side(const Bm2Args &a, hipStream_t st) {
         int cus = 0;
         e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
         if (e != hipSuccess) return e;
-        // one block per resident slot: the DSX_TIMELINE census showed all 12 reported blocks of
-        // the C2 kernel co-resident (3072 on 256 CUs) and 12/CU beat 11/CU by 5% (C2, C4) while
-        // 13/CU ran a second generation.  DSX_BLOCKS_PER_CU_ADJ (e.g. -1) adjusts for tuning.
+        // the residency bm2_grid plans with; DSX_BLOCKS_PER_CU_ADJ (e.g. -1) adjusts it for tuning
         const char *adj = getenv("DSX_BLOCKS_PER_CU_ADJ");
         const int nbr = nb + (adj ? atoi(adj) : 0);
         blocks_per_cu[dev] = nbr > 1 ? nbr : 1;
         num_cu[dev] = cus > 0 ? cus : 1;
     }
-    const long T = (long)a.strip_count * a.nframes * a.H;
-    long grid = (long)blocks_per_cu[dev] * num_cu[dev];
-    // Small frames: when a full grid leaves each block fewer rows than its (2R+1)-row segment
-    // start, two thirds of the residency measured faster (C1 single frame, 2.97 rows per block at
-    // 12 blocks/CU: 22.9 -> 20.6 us at 8 blocks/CU; grids of 1792-3072 otherwise within 2 %).
-    // C2-C5 keep the full grid.  DSX_SMALL_GRID=0 disables.
+    // the switches of bm2_grid's two reduced-grid rules: DSX_SMALL_GRID=0 / DSX_FLIGHT_GRID=0 disable one
     static const bool small_grid = [] {
         const char *e = getenv("DSX_SMALL_GRID");
         return !(e && *e == '0');
     }();
-    // The SAD1 kernels (ABS) are measured fastest on the full grid (C1: 14.9 us at two thirds, 13.6 us
-    // full; tools/c1_grid.sh), so the rule applies to the pair / SSD layouts only.
-    if (small_grid && !ABS && T < grid * (2L * R + 1) && blocks_per_cu[dev] >= 3) grid = (long)num_cu[dev] * (blocks_per_cu[dev] * 2 / 3);
-    // in_flight handles, one-wave blocks: two thirds of the residency.  A launch that shares the device with two others
-    // gains nothing from a block per resident slot, and every block pays a (2R+1)-row segment start for its rows (C2:
-    // about 20 rows behind a 9-row start at 3072 blocks).  Parent library, three frames in flight, grids of 1, 2/3,
-    // 1/2, 1/3 of the residency (profiles/sref_ab.txt): C2 44.5k / 46.0k / 46.8k / 45.3k Mpix/s, C4 22.4k / 22.9k /
-    // 21.7k / 22.5k, C2r 23.1k / 23.3k / 23.0k / 22.9k, C1 33.2k / 36.6k / 37.7k and 24.8k / 35.9k; half loses on C4.
-    // The two- and four-wave blocks (6 and 4 per CU) keep the full grid: C5 20.57k / 20.55k / 20.29k / 16.9k,
-    // C3 7.18k / 7.25k / 7.26k / 6.41k.  Lone-frame handles keep the full grid.  DSX_FLIGHT_GRID=0 disables.
     static const bool flight_grid = [] {
         const char *e = getenv("DSX_FLIGHT_GRID");
         return !(e && *e == '0');
     }();
-    // The plain left pass of the pair layout (SIDE 0, C2's kernel) takes half of the residency: with the output stores
-    // behind the staging its optimum moved (grids of 1, 2/3, 1/2: 46.5k / 47.7k / 48.1k Mpix/s, three runs each within
-    // 0.1k; profiles/stageahead_ab.txt).  The LR passes lose at half (C4 above), and the SAD1 layout, which gained there
-    // in this sweep (C1 38.8k -> 39.8k), once fell to 24.8k on one of two runs at half and stays on two thirds.
-    if (flight_grid && a.in_flight && NW == 1 && blocks_per_cu[dev] >= 3) {
-        const bool half = !SSD && SIDE == 0;
-        const long g23 = (long)num_cu[dev] * (half ? blocks_per_cu[dev] / 2 : blocks_per_cu[dev] * 2 / 3);
-        if (g23 < grid) grid = g23;
-    }
-    if (a.grid_override > 0) grid = a.grid_override;
-    if (grid > T) grid = T;
-    if (grid < 1) grid = 1;
+    const Bm2Grid plan = bm2_grid(blocks_per_cu[dev], num_cu[dev], R, NW, SSD, SIDE, ABS, (long)a.strip_count * a.nframes * a.H,
+                                  a.nframes, a.in_flight != 0, a.grid_override, small_grid, flight_grid);
+    const long grid = plan.grid;
     static const bool verbose = getenv("DSX_VERBOSE") != nullptr;  // diagnostics: read once
     if (verbose)
         fprintf(stderr, "[dsx] bm2<R=%d,SSD=%d,NW=%d,SIDE=%d> grid %ld (%d/CU) smem %d\n", R, (int)SSD, NW, SIDE, grid,
                 blocks_per_cu[dev], SM);
-    // age levels: with one block per resident slot, block b is the (b / num_cu)-th block its CU
-    // received, and co-resident waves of a SIMD differ in age (issue arbitration) by that rank
     Bm2Args la = a;
-    la.nlev = 1;
-    if (grid == (long)blocks_per_cu[dev] * num_cu[dev] && a.nframes == 1) {  // batches: equal weights
-        const int lv = blocks_per_cu[dev] * NW / 4;
-        la.nlev = lv < 1 ? 1 : (lv > 4 ? 4 : lv);
-    }
+    la.nlev = plan.nlev;
     {
-        constexpr int NJ4 = (G::NJ + 3) / 4, NC4 = (G::NC + 3) / 4, NC = G::NC;
-        const int W = a.W, m = a.m;
+        const Bm2Interval fi = bm2_fast_interval(SIDE, R, G::NC, G::NJ, a.W, a.m);
         PartKey k;
         memset(&k, 0, sizeof(k));
         k.dev = dev, k.NG = (int)grid, k.S = a.strip_count, k.sb = a.strip_begin, k.nframes = a.nframes, k.H = a.H;
-        if (SIDE == 1) {
-            k.XL = std::max(R - m, R);
-            k.XU = std::min(W - 1 - 4 * NJ4 + R - m, W - 1 + R - 4 * NC4 + 1);
-        } else {
-            k.XL = std::max(4 * NJ4 + R + m - NC + 1, R);
-            k.XU = std::min(W - 1 + R + m - NC + 1, W - 1 + R - 4 * NC4 + 1);
-        }
-        k.w8 = a.slow_w8, k.nlev = la.nlev;
+        k.XL = fi.XL, k.XU = fi.XU, k.w8 = a.slow_w8, k.nlev = la.nlev;
         for (int i = 0; i < 4; ++i) k.w[i] = la.nlev > 1 ? a.agew[i] : 64;
         e = bm2_partition_dev(k, G::TX, &la.part);
         if (e != hipSuccess) return e;

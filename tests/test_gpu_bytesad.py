@@ -23,6 +23,8 @@ from oracle.cref import CRef
 from oracle.sgbm_post import wta_sgbm
 from oracle.stereo_bm import cost_volume, right_argmin
 
+import fused_geometry as fg
+
 pytestmark = pytest.mark.gpu
 
 H, W = 40, 256
@@ -53,12 +55,6 @@ def _inputs(m, D):
     return {"random": (L, R), "carry_cols": (white, cols), "carry_rows": (white, rows)}
 
 
-def _check(got, want, what):
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, (f"{what}: {len(bad)} of {got.size} pixels differ, first {bad[:4].tolist()}: "
-                           f"got {got[tuple(bad[0])]} want {want[tuple(bad[0])]}")
-
-
 def _left(torch, pairs, wants, what, **kw):
     """One matcher per grid, every input through it."""
     from depthestimation_amd.matcher import HipBlockMatcher
@@ -66,7 +62,7 @@ def _left(torch, pairs, wants, what, **kw):
         mt = HipBlockMatcher(grid_blocks=g, **kw)
         try:
             for name, (L, R) in pairs.items():
-                _check(mt.compute(L, R), wants[name], f"{what} grid_blocks={g} input={name}")
+                fg.check(mt.compute(L, R), wants[name], f"{what} grid_blocks={g} input={name}")
         finally:
             mt.close()
 
@@ -97,7 +93,7 @@ def test_pair_layout_sides(torch_dev, cref, bs, D, m):
                 out = torch.empty((H, W), dtype=torch.int16, device="cuda")
                 mt.right_map_device(torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda(), out)
                 torch.cuda.synchronize()
-                _check(out.cpu().numpy().astype(np.int32), right_argmin(vols[name], m),
+                fg.check(out.cpu().numpy().astype(np.int32), right_argmin(vols[name], m),
                        f"right map grid_blocks={g} input={name}")
         finally:
             mt.close()

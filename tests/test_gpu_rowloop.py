@@ -32,6 +32,8 @@ from oracle.cref import CRef
 from oracle.sgbm_post import wta_sgbm
 from oracle.stereo_bm import cost_volume, right_argmin
 
+import fused_geometry as fg
+
 pytestmark = pytest.mark.gpu
 
 W = 256
@@ -62,18 +64,6 @@ def _inputs(m, D, H=40, seed=0):
     return {"random": (L, R), "carry_cols": (white, cols), "carry_rows": (white, rows)}
 
 
-def _check(got, want, what):
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, (f"{what}: {len(bad)} of {got.size} pixels differ, first {bad[:4].tolist()}: "
-                           f"got {got[tuple(bad[0])]} want {want[tuple(bad[0])]}")
-
-
-def _check_both(fixed, flt, want, what):
-    """int16 x16 map and float map (x16 / 16) against the oracle's x16 map."""
-    _check(fixed.cpu().numpy(), want, what + " fixed")
-    _check(flt.cpu().numpy(), want.astype(np.float32) / np.float32(16), what + " float")
-
-
 def _left(torch, pairs, wants, what, grids=GRIDS, **kw):
     """One matcher per grid, every input through it, both outputs checked."""
     from depthestimation_amd.matcher import HipBlockMatcher
@@ -86,7 +76,7 @@ def _left(torch, pairs, wants, what, grids=GRIDS, **kw):
                 fl = torch.empty((H, W), dtype=torch.float32, device="cuda")
                 mt.compute_device(torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda(), out_fixed=fx, out_float=fl)
                 torch.cuda.synchronize()
-                _check_both(fx, fl, wants[name], f"{what} grid_blocks={g} input={name}")
+                fg.check_maps(fx, fl, wants[name], f"{what} grid_blocks={g} input={name}")
         finally:
             mt.close()
 
@@ -141,7 +131,7 @@ def test_all_sides(torch_dev, cref, bs, m):
                 out = torch.empty(L.shape, dtype=torch.int16, device="cuda")
                 mt.right_map_device(torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda(), out)
                 torch.cuda.synchronize()
-                _check(out.cpu().numpy().astype(np.int32), right_argmin(vols[name], m),
+                fg.check(out.cpu().numpy().astype(np.int32), right_argmin(vols[name], m),
                        f"right map grid_blocks={g} input={name}")
         finally:
             mt.close()
@@ -172,12 +162,12 @@ def test_two_frames_and_padded_rows(torch_dev, cref, pad):
                 mt.compute_batch_device(dL, dR, out_fixed=fx, out_float=fl)
                 torch.cuda.synchronize()
                 for i in range(2):
-                    _check_both(fx[i], fl[i], wants[i], f"batch {what} pad={pad} grid_blocks={g} frame={i}")
+                    fg.check_maps(fx[i], fl[i], wants[i], f"batch {what} pad={pad} grid_blocks={g} frame={i}")
                 fx1 = torch.empty((H, W), dtype=torch.int16, device="cuda")
                 fl1 = torch.empty((H, W), dtype=torch.float32, device="cuda")
                 mt.compute_device(dL[1], dR[1], out_fixed=fx1, out_float=fl1)
                 torch.cuda.synchronize()
-                _check_both(fx1, fl1, wants[1], f"single {what} pad={pad} grid_blocks={g}")
+                fg.check_maps(fx1, fl1, wants[1], f"single {what} pad={pad} grid_blocks={g}")
             finally:
                 mt.close()
 
@@ -200,7 +190,7 @@ def test_three_in_flight(torch_dev, cref):
             handles[i % 3].compute_device(*dev[i % 3], out_fixed=fx[i], out_float=fl[i], stream=streams[i % 3])
         torch.cuda.synchronize()
         for i in range(6):
-            _check_both(fx[i], fl[i], wants[i % 3], f"in_flight handle {i % 3} call {i // 3}")
+            fg.check_maps(fx[i], fl[i], wants[i % 3], f"in_flight handle {i % 3} call {i // 3}")
     finally:
         for h in handles:
             h.close()

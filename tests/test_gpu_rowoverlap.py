@@ -5,7 +5,7 @@ folded once settled); the cases guard the segment shapes below, at w
 
 A segment's first step has no epilogue and one epilogue drains the segment behind its last step, so what decides
 the code path is the segment length: 1 row is init + drain only, 2 rows have one overlapped step.  The cases are
-chosen by it from a restatement of the host partition (csrc/dsx_partition.h, equal block weights), and every
+chosen by it from the launch geometry restated in tests/fused_geometry.py, and every
 case asserts from that restatement that the classes it is there for occur: segments of 1, 2, 3 and 20 or more
 rows, blocks that own several segments in a row (they go on into the next strip or frame), strips cut inside
 (a segment that starts below row 0).
@@ -22,7 +22,8 @@ import numpy as np
 import pytest
 
 from depthestimation_amd.synthetic import binary_pair, stereo_pair
-from oracle.cref import CRef
+
+import fused_geometry as fg
 
 pytestmark = pytest.mark.gpu
 
@@ -38,104 +39,22 @@ def torch_dev():
     return torch
 
 
-_CREF = []
-_WANT = {}
-
-
-def _want(key, L, R, m, d, bs, u, sp):
-    """Oracle maps, computed once per (input, parameters) and shared by the tests."""
-    k = (key, m, d, bs, u, sp)
-    if k not in _WANT:
-        if not _CREF:
-            _CREF.append(CRef())
-        _WANT[k] = _CREF[0](L, R, m, d, bs, "sad", u, -1, sp)
-    return _WANT[k]
-
-
-# ---- host partition, restated (bm2_partition with one age level: every block weighs the same) --------
-
-def _partition(NG, S, sb, nf, H, XL, XU, TX=32, w8=11):
-    NS = S * nf
-    if NG < NS:
-        return [b * NS * H // NG for b in range(NG + 1)]
-    slo = min(max((XL + TX - 1) // TX - sb, 0), S)
-    shi = min(max(XU // TX - sb + 1, slo), S)
-    if w8 < 8 or NG * 8 < NS * w8 + 8 * NS:
-        w8 = 8
-    ex = w8 - 8
-    Pf = lambda s: 8 * s + ex * (min(s, slo) + max(0, s - shi))  # noqa: E731
-    Uf = Pf(S)
-    U = Uf * nf
-    P = lambda g: (g // S) * Uf + Pf(g % S)  # noqa: E731
-    start, b = [], 0
-    for g in range(NS + 1):
-        while b < NG and b * U < P(g) * NG:
-            b += 1
-        start.append(b)
-    part = [0] * (NG + 1)
-    for g in range(NS):
-        qd = start[g + 1] - start[g]
-        for bb in range(start[g], start[g + 1] + 1):
-            part[bb] = g * H + (bb - start[g]) * H // qd
-    part[NG] = NS * H
-    return part
-
-
 def _blocks(H, gb, W=W0, m=M, nf=1, R=BS // 2, d=D):
-    """Per block of a left-pass launch its segments (frame, strip, first row, row count), in order."""
-    NC, Dp = 32 + 2 * R, 128
-    NJ4, NC4 = (NC + Dp + 3) // 4, (NC + 3) // 4
-    xlo, xhi = max(0, m + d - 1), min(W - 1, W - 1 + m)
-    sb = xlo // 32
-    S = xhi // 32 + 1 - sb
-    XL = max(4 * NJ4 + R + m - NC + 1, R)
-    XU = min(W - 1 + R + m - NC + 1, W - 1 + R - 4 * NC4 + 1)
-    T = S * nf * H
-    NG = min(gb, T) if gb > 0 else T  # the resident capacity (thousands of blocks) exceeds T at these sizes
-    part = _partition(NG, S, sb, nf, H, XL, XU)
-    out = []
-    for b in range(NG):
-        it, lin1, segs = part[b], part[b + 1], []
-        while it < lin1:
-            sidx, yb = it // H, it % H
-            ye = min(H, yb + lin1 - it)
-            segs.append((sidx // S, sidx % S, yb, ye - yb))
-            it += ye - yb
-        out.append(segs)
-    assert sum(s[3] for segs in out for s in segs) == T
-    return out
+    """Per block of a left-pass launch its segments (fused_geometry.Seg), in order."""
+    return fg.blocks(H, gb, W, m, nf, R, d)
 
 
 def _kinds(blocks):
     segs = [s for b in blocks for s in b]
     k = {name for name, f in (("one", lambda n: n == 1), ("two", lambda n: n == 2), ("three", lambda n: n == 3),
-                              ("long", lambda n: n >= 20)) if any(f(s[3]) for s in segs)}
-    if any(len(b) > 1 and any(p[1] != q[1] and p[0] == q[0] for p, q in zip(b, b[1:])) for b in blocks):
+                              ("long", lambda n: n >= 20)) if any(f(s.rows) for s in segs)}
+    if any(len(b) > 1 and any(p.strip != q.strip and p.frame == q.frame for p, q in zip(b, b[1:])) for b in blocks):
         k.add("next_strip")  # a block goes on into the next strip: two segments in a row
-    if any(len(b) > 1 and any(p[0] != q[0] for p, q in zip(b, b[1:])) for b in blocks):
+    if any(len(b) > 1 and any(p.frame != q.frame for p, q in zip(b, b[1:])) for b in blocks):
         k.add("next_frame")
-    if any(s[2] > 0 for s in segs):
+    if any(s.y0 > 0 for s in segs):
         k.add("cut")  # a strip cut inside: the segment starts below row 0
     return k
-
-
-# ---- comparison --------------------------------------------------------------------------------------
-
-def _check(got, want, what):
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, (f"{what}: {len(bad)} of {got.size} pixels differ, first {bad[:4].tolist()}: "
-                           f"got {got[tuple(bad[0])]} want {want[tuple(bad[0])]}")
-
-
-def _check_maps(fixed, flt, want, what, fmode="fixed"):
-    wf = want["fixed"]
-    if fixed is not None:
-        _check(fixed.cpu().numpy(), wf, what + " fixed")
-    if flt is not None:
-        if fmode == "fixed":
-            _check(flt.cpu().numpy(), wf.astype(np.float32) / np.float32(16), what + " float")
-        else:
-            _check(flt.cpu().numpy().view(np.int32), want["parabola"].view(np.int32), what + " float (parabola, bits)")
 
 
 def _run(torch, L, R, want, what, grids, fmode="fixed", **kw):
@@ -148,7 +67,7 @@ def _run(torch, L, R, want, what, grids, fmode="fixed", **kw):
             fl = torch.empty(L.shape, dtype=torch.float32, device="cuda")
             mt.compute_device(dL, dR, out_fixed=fx, out_float=fl)
             torch.cuda.synchronize()
-            _check_maps(fx, fl, want, f"{what} grid_blocks={g}", fmode)
+            fg.check_maps(fx, fl, want, f"{what} grid_blocks={g}", fmode)
         finally:
             mt.close()
 
@@ -162,7 +81,7 @@ def _all_modes(torch, key, L, R, grids, what, m=M, d=D, bs=BS, modes=(("fixed", 
     kw = dict(BASE, min_disp=m, num_disp=d, block_size=bs)
     for u in us:
         for fmode, sp in modes:
-            want = _want(key, L, R, m, d, bs, u, sp)
+            want = fg.want(key, L, R, m, d, bs, u, sp)
             _run(torch, L, R, want, f"{what} u={u} {fmode} subpixel={sp}", grids, fmode=fmode, uniqueness_ratio=u, subpixel=sp, **kw)
 
 
@@ -184,9 +103,9 @@ def test_segment_lengths(torch_dev, H, gb):
     blocks = _blocks(H, gb)
     assert CLAIMS[(H, gb)] <= _kinds(blocks), (H, gb, blocks)
     if (H, gb) == (7, 4):
-        assert [[s[3] for s in b] for b in blocks] == [[7, 1], [6, 3], [4, 5], [2, 7]]
+        assert [[s.rows for s in b] for b in blocks] == [[7, 1], [6, 3], [4, 5], [2, 7]]
     if (H, gb) == (41, 4):
-        assert [[s[3] for s in b] for b in blocks] == [[41, 10], [31, 20], [21, 30], [11, 41]]
+        assert [[s.rows for s in b] for b in blocks] == [[41, 10], [31, 20], [21, 30], [11, 41]]
     L, R = _pair(H)
     _all_modes(torch_dev, ("random", H), L, R, (gb,), f"H={H} random")
     Lb, Rb = binary_pair(H, W0, M, D, seed=91 + H)[:2]  # ties between neighbouring disparities: quotient 8
@@ -210,7 +129,7 @@ def test_constant_images(torch_dev):
     H = 7
     L = np.full((H, W0), 93, np.uint8)
     R = np.full((H, W0), 93, np.uint8)
-    want = _want(("const", H), L, R, M, D, BS, 0, True)
+    want = fg.want(("const", H), L, R, M, D, BS, 0, True)
     band = want["fixed"][:, D - 1:]
     assert np.all(band == 0)
     _all_modes(torch_dev, ("const", H), L, R, (0, 1, 4), "constant")
@@ -235,7 +154,7 @@ def test_batch_of_two_frames(torch_dev, H):
         kinds |= _kinds(_blocks(H, g, nf=2))
     assert "next_frame" in kinds and "next_strip" in kinds
     for u in (0, 10):
-        wants = [_want(("random", H) if i == 0 else ("rolled", H), L, R, M, D, BS, u, True) for i, (L, R) in enumerate(fr)]
+        wants = [fg.want(("random", H) if i == 0 else ("rolled", H), L, R, M, D, BS, u, True) for i, (L, R) in enumerate(fr)]
         assert np.any(wants[0]["fixed"] != wants[1]["fixed"])
         for g in (0, 1, 3, 7):
             mt = HipBlockMatcher(grid_blocks=g, uniqueness_ratio=u, **BASE)
@@ -245,7 +164,7 @@ def test_batch_of_two_frames(torch_dev, H):
                 mt.compute_batch_device(dL, dR, out_fixed=fx, out_float=fl)
                 torch.cuda.synchronize()
                 for i in range(2):
-                    _check_maps(fx[i], fl[i], wants[i], f"batch H={H} u={u} grid_blocks={g} frame={i}")
+                    fg.check_maps(fx[i], fl[i], wants[i], f"batch H={H} u={u} grid_blocks={g} frame={i}")
             finally:
                 mt.close()
 
@@ -256,7 +175,7 @@ def test_in_flight_handles(torch_dev):
     from depthestimation_amd.matcher import HipBlockMatcher
     H = 24
     fr = [_pair(H), binary_pair(H, W0, M, D, seed=91 + H)[:2]]
-    wants = [_want(("random", H), *fr[0], M, D, BS, 0, True), _want(("binary", H), *fr[1], M, D, BS, 0, True)]
+    wants = [fg.want(("random", H), *fr[0], M, D, BS, 0, True), fg.want(("binary", H), *fr[1], M, D, BS, 0, True)]
     dev = [(torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda()) for L, R in fr]
     handles = [HipBlockMatcher(in_flight=True, uniqueness_ratio=0, **BASE) for _ in range(2)]
     streams = [torch.cuda.Stream() for _ in range(2)]
@@ -268,7 +187,7 @@ def test_in_flight_handles(torch_dev):
             handles[i % 2].compute_device(*dev[i % 2], out_fixed=fx[i], out_float=fl[i], stream=streams[i % 2])
         torch.cuda.synchronize()
         for i in range(4):
-            _check_maps(fx[i], fl[i], wants[i % 2], f"in_flight handle {i % 2} call {i // 2}")
+            fg.check_maps(fx[i], fl[i], wants[i % 2], f"in_flight handle {i % 2} call {i // 2}")
     finally:
         for h in handles:
             h.close()

@@ -7,9 +7,9 @@ The paired tail left a row step's scan results (winner, its cost, valid bit, the
 lanes of a pixel; the first row of a pair kept them across the next step, the second row's tail finished both
 rows at once (lane h = 0 the kept row, h = 1 its own), and a segment's unpaired last row ran the tail on the
 h = 0 lanes alone.  Rows were paired by their offset in the segment, so what decided the form was the segment
-length: the cases below are chosen by it, from a restatement of the host partition (csrc/dsx_partition.h,
-equal block weights), and guard a tail that holds anything across row steps.  The quotient's cases are the tail classes (quotients 8, 0 and below 0, rows that take
-no step) and disparity ranges of one, two and four waves per block.
+length: the cases below are chosen by it, from the launch geometry restated in tests/fused_geometry.py, and guard
+a tail that holds anything across row steps.  The quotient's cases are the tail classes (quotients 8, 0 and
+below 0, rows that take no step) and disparity ranges of one, two and four waves per block.
 
 Every comparison is bit for bit over all pixels against the C oracle (oracle/cref.py): the int16 x16 map and
 the float map - float mode 'fixed' against x16 / 16 (exact in f32), 'parabola' by bit pattern.
@@ -31,6 +31,8 @@ from depthestimation_amd.synthetic import binary_pair, stereo_pair
 from oracle.cref import CRef
 from oracle.stereo_bm import cost_volume
 
+import fused_geometry as fg
+
 pytestmark = pytest.mark.gpu
 
 M, D, BS, W0 = 0, 128, 9, 256
@@ -50,81 +52,14 @@ def cref():
     return CRef()
 
 
-# ---- host partition, restated (bm2_partition with one age level: every block weighs the same) --------
-
-def _partition(NG, S, sb, nf, H, XL, XU, TX=32, w8=11):
-    NS = S * nf
-    if NG < NS:
-        return [b * NS * H // NG for b in range(NG + 1)]
-    slo = min(max((XL + TX - 1) // TX - sb, 0), S)
-    shi = min(max(XU // TX - sb + 1, slo), S)
-    if w8 < 8 or NG * 8 < NS * w8 + 8 * NS:
-        w8 = 8
-    ex = w8 - 8
-    Pf = lambda s: 8 * s + ex * (min(s, slo) + max(0, s - shi))  # noqa: E731
-    Uf = Pf(S)
-    U = Uf * nf
-    P = lambda g: (g // S) * Uf + Pf(g % S)  # noqa: E731
-    start, b = [], 0
-    for g in range(NS + 1):
-        while b < NG and b * U < P(g) * NG:
-            b += 1
-        start.append(b)
-    part = [0] * (NG + 1)
-    for g in range(NS):
-        qd = start[g + 1] - start[g]
-        for bb in range(start[g], start[g + 1] + 1):
-            part[bb] = g * H + (bb - start[g]) * H // qd
-    part[NG] = NS * H
-    return part
-
-
 def _segments(H, gb, W=W0, m=M, nf=1, R=BS // 2):
     """Lengths of the segments (runs of rows of one strip in one block) of a left-pass launch."""
-    NC, Dp = 32 + 2 * R, 128
-    NJ4, NC4 = (NC + Dp + 3) // 4, (NC + 3) // 4
-    xlo, xhi = max(0, m + D - 1), min(W - 1, W - 1 + m)
-    sb = xlo // 32
-    S = xhi // 32 + 1 - sb
-    XL = max(4 * NJ4 + R + m - NC + 1, R)
-    XU = min(W - 1 + R + m - NC + 1, W - 1 + R - 4 * NC4 + 1)
-    T = S * nf * H
-    NG = min(gb, T) if gb > 0 else T  # the resident capacity (thousands of blocks) exceeds T at these sizes
-    part = _partition(NG, S, sb, nf, H, XL, XU)
-    segs = []
-    for b in range(NG):
-        it, lin1 = part[b], part[b + 1]
-        while it < lin1:
-            yb = it % H
-            ye = min(H, yb + lin1 - it)
-            segs.append(ye - yb)
-            it += ye - yb
-    assert sum(segs) == T
-    return segs
+    return [s.rows for b in fg.blocks(H, gb, W, m, nf, R, D) for s in b]
 
 
 def _kinds(segs):
     return {k for k, f in (("one", lambda n: n == 1), ("even", lambda n: n % 2 == 0), ("odd3", lambda n: n % 2 == 1 and n >= 3))
             if any(f(n) for n in segs)}
-
-
-# ---- comparison --------------------------------------------------------------------------------------
-
-def _check(got, want, what):
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, (f"{what}: {len(bad)} of {got.size} pixels differ, first {bad[:4].tolist()}: "
-                           f"got {got[tuple(bad[0])]} want {want[tuple(bad[0])]}")
-
-
-def _check_maps(fixed, flt, want, what, fmode="fixed"):
-    wf = want["fixed"]
-    if fixed is not None:
-        _check(fixed.cpu().numpy(), wf, what + " fixed")
-    if flt is not None:
-        if fmode == "fixed":
-            _check(flt.cpu().numpy(), wf.astype(np.float32) / np.float32(16), what + " float")
-        else:
-            _check(flt.cpu().numpy().view(np.int32), want["parabola"].view(np.int32), what + " float (parabola, bits)")
 
 
 def _run(torch, L, R, want, what, grids, fmode="fixed", outs="both", **kw):
@@ -136,7 +71,7 @@ def _run(torch, L, R, want, what, grids, fmode="fixed", outs="both", **kw):
             fl = torch.empty(L.shape, dtype=torch.float32, device="cuda") if outs in ("both", "float") else None
             mt.compute_device(torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda(), out_fixed=fx, out_float=fl)
             torch.cuda.synchronize()
-            _check_maps(fx, fl, want, f"{what} grid_blocks={g}", fmode)
+            fg.check_maps(fx, fl, want, f"{what} grid_blocks={g}", fmode)
         finally:
             mt.close()
 
@@ -211,12 +146,12 @@ def test_no_leak_across_frames(torch_dev, cref, H):
                 mt.compute_batch_device(dL, dR, out_fixed=fx, out_float=fl)
                 torch.cuda.synchronize()
                 for i in range(2):
-                    _check_maps(fx[i], fl[i], wants[i], f"batch H={H} u={u} grid_blocks={g} frame={i}")
+                    fg.check_maps(fx[i], fl[i], wants[i], f"batch H={H} u={u} grid_blocks={g} frame={i}")
                 for i in range(2):
                     f1 = torch.empty((H, W0), dtype=torch.int16, device="cuda")
                     mt.compute_device(dL[i], dR[i], out_fixed=f1)
                     torch.cuda.synchronize()
-                    _check_maps(f1, None, wants[i], f"single H={H} u={u} grid_blocks={g} frame={i}")
+                    fg.check_maps(f1, None, wants[i], f"single H={H} u={u} grid_blocks={g} frame={i}")
             finally:
                 mt.close()
 
@@ -379,7 +314,7 @@ def test_three_in_flight(torch_dev, cref):
             handles[i % 3].compute_device(*dev[i % 3], out_fixed=fx[i], out_float=fl[i], stream=streams[i % 3])
         torch.cuda.synchronize()
         for i in range(6):
-            _check_maps(fx[i], fl[i], wants[i % 3], f"in_flight handle {i % 3} call {i // 3}")
+            fg.check_maps(fx[i], fl[i], wants[i % 3], f"in_flight handle {i % 3} call {i // 3}")
     finally:
         for h in handles:
             h.close()

@@ -33,6 +33,8 @@ from oracle.cref import CRef
 from oracle.sgbm_post import wta_sgbm
 from oracle.stereo_bm import cost_volume, right_argmin
 
+import fused_geometry as fg
+
 pytestmark = pytest.mark.gpu
 
 GRIDS = (0, 1, 7)
@@ -74,22 +76,6 @@ def _tie_inputs(m, D, H, W):
             "period8": _periodic(8, H, W, 8), "period64": _periodic(64, H, W, 64)}
 
 
-def _check(got, want, what):
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, (f"{what}: {len(bad)} of {got.size} pixels differ, first {bad[:4].tolist()}: "
-                           f"got {got[tuple(bad[0])]} want {want[tuple(bad[0])]}")
-
-
-def _check_maps(fixed, flt, want, what, fmode="fixed"):
-    """want: oracle dict (C oracle) or its x16 map alone (float mode 'fixed' only)."""
-    wf = want["fixed"] if isinstance(want, dict) else want
-    _check(fixed.cpu().numpy(), wf, what + " fixed")
-    if fmode == "fixed":
-        _check(flt.cpu().numpy(), wf.astype(np.float32) / np.float32(16), what + " float")
-    else:
-        _check(flt.cpu().numpy().view(np.int32), want["parabola"].view(np.int32), what + " float (parabola, bits)")
-
-
 def _left(torch, pairs, wants, what, grids=GRIDS, fmode="fixed", **kw):
     """One matcher per grid, every input through it, both outputs checked."""
     from depthestimation_amd.matcher import HipBlockMatcher
@@ -101,7 +87,7 @@ def _left(torch, pairs, wants, what, grids=GRIDS, fmode="fixed", **kw):
                 fl = torch.empty(L.shape, dtype=torch.float32, device="cuda")
                 mt.compute_device(torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda(), out_fixed=fx, out_float=fl)
                 torch.cuda.synchronize()
-                _check_maps(fx, fl, wants[name], f"{what} grid_blocks={g} input={name}", fmode)
+                fg.check_maps(fx, fl, wants[name], f"{what} grid_blocks={g} input={name}", fmode)
         finally:
             mt.close()
 
@@ -119,7 +105,7 @@ def _right(torch, pairs, vols, m, what, **base):
                 out = torch.empty(L.shape, dtype=torch.int16, device="cuda")
                 mt.right_map_device(torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda(), out)
                 torch.cuda.synchronize()
-                _check(out.cpu().numpy().astype(np.int32), right_argmin(vols[name], m),
+                fg.check(out.cpu().numpy().astype(np.int32), right_argmin(vols[name], m),
                        f"{what} right map grid_blocks={g} input={name}")
         finally:
             mt.close()
@@ -245,12 +231,12 @@ def test_two_frames_and_padded_rows(torch_dev, cref, pad):
                 mt.compute_batch_device(dL, dR, out_fixed=fx, out_float=fl)
                 torch.cuda.synchronize()
                 for i in range(2):
-                    _check_maps(fx[i], fl[i], wants[i], f"batch {what} pad={pad} grid_blocks={g} frame={i}")
+                    fg.check_maps(fx[i], fl[i], wants[i], f"batch {what} pad={pad} grid_blocks={g} frame={i}")
                 fx1 = torch.empty((H, W), dtype=torch.int16, device="cuda")
                 fl1 = torch.empty((H, W), dtype=torch.float32, device="cuda")
                 mt.compute_device(dL[1], dR[1], out_fixed=fx1, out_float=fl1)
                 torch.cuda.synchronize()
-                _check_maps(fx1, fl1, wants[1], f"single {what} pad={pad} grid_blocks={g}")
+                fg.check_maps(fx1, fl1, wants[1], f"single {what} pad={pad} grid_blocks={g}")
             finally:
                 mt.close()
 
@@ -276,7 +262,7 @@ def test_three_in_flight(torch_dev, cref, kw, u, lr):
             handles[i % 3].compute_device(*dev[i % 3], out_fixed=fx[i], out_float=fl[i], stream=streams[i % 3])
         torch.cuda.synchronize()
         for i in range(6):
-            _check_maps(fx[i], fl[i], wants[i % 3], f"in_flight handle {i % 3} call {i // 3}")
+            fg.check_maps(fx[i], fl[i], wants[i % 3], f"in_flight handle {i % 3} call {i // 3}")
     finally:
         for h in handles:
             h.close()

@@ -7,8 +7,8 @@ from the source.
 
 What these forms can get wrong is a row of the init (clamped into the frame at both ends, rows past 2R zero), the
 column chunk a read belongs to (the last one partial at odd radii), and the block's first and last unit.  So the
-cases are chosen by where segments start and how long they are, from a restatement of the host partition
-(csrc/dsx_partition.h, equal block weights) and of the kernel's test for the unaligned-dword copy ("fast" below; the
+cases are chosen by where segments start and how long they are, from the launch geometry restated in
+tests/fused_geometry.py (the host partition and the kernel's test for the unaligned-dword copy, "fast" below; the
 others take clamped bytes), and every case asserts from that restatement that the classes it is there for occur.
 
 Every comparison is bit for bit over all pixels against the C oracle (oracle/cref.py): the int16 x16 map and the
@@ -23,7 +23,8 @@ import numpy as np
 import pytest
 
 from depthestimation_amd.synthetic import binary_pair, stereo_pair
-from oracle.cref import CRef
+
+import fused_geometry as fg
 
 pytestmark = pytest.mark.gpu
 
@@ -39,83 +40,9 @@ def torch_dev():
     return torch
 
 
-_CREF = []
-_WANT = {}
-
-
-def _want(key, L, R, m, d, bs, u, sp, lr=-1):
-    """Oracle maps, computed once per (input, parameters) and shared by the tests."""
-    k = (key, m, d, bs, u, sp, lr)
-    if k not in _WANT:
-        if not _CREF:
-            _CREF.append(CRef())
-        _WANT[k] = _CREF[0](L, R, m, d, bs, "sad", u, lr, sp)
-    return _WANT[k]
-
-
-# ---- host partition, restated (bm2_partition with one age level: every block weighs the same) --------
-
-def _partition(NG, S, sb, nf, H, XL, XU, TX=32, w8=11):
-    NS = S * nf
-    if NG < NS:
-        return [b * NS * H // NG for b in range(NG + 1)]
-    slo = min(max((XL + TX - 1) // TX - sb, 0), S)
-    shi = min(max(XU // TX - sb + 1, slo), S)
-    if w8 < 8 or NG * 8 < NS * w8 + 8 * NS:
-        w8 = 8
-    ex = w8 - 8
-    Pf = lambda s: 8 * s + ex * (min(s, slo) + max(0, s - shi))  # noqa: E731
-    Uf = Pf(S)
-    U = Uf * nf
-    P = lambda g: (g // S) * Uf + Pf(g % S)  # noqa: E731
-    start, b = [], 0
-    for g in range(NS + 1):
-        while b < NG and b * U < P(g) * NG:
-            b += 1
-        start.append(b)
-    part = [0] * (NG + 1)
-    for g in range(NS):
-        qd = start[g + 1] - start[g]
-        for bb in range(start[g], start[g + 1] + 1):
-            part[bb] = g * H + (bb - start[g]) * H // qd
-    part[NG] = NS * H
-    return part
-
-
-def _dp(d):
-    """Disparities per block: SAD1 (one per lane) up to 64, else pairs in one, two or four waves."""
-    return 64 if d <= 64 else (128 if d <= 128 else (256 if d <= 256 else 512))
-
-
 def _blocks(H, gb, W=W0, m=M, nf=1, R=BS // 2, d=D):
-    """Per block of a left-pass launch its segments (frame, strip, first row, row count, fast), in order."""
-    NC, Dp = 32 + 2 * R, _dp(d)
-    NJ4, NC4 = (NC + Dp + 3) // 4, (NC + 3) // 4
-    xlo, xhi = max(0, m + d - 1), min(W - 1, W - 1 + m)
-    sb = xlo // 32
-    S = xhi // 32 + 1 - sb
-    XL = max(4 * NJ4 + R + m - NC + 1, R)
-    XU = min(W - 1 + R + m - NC + 1, W - 1 + R - 4 * NC4 + 1)
-    T = S * nf * H
-    NG = min(gb, T) if gb > 0 else T  # the resident capacity (thousands of blocks) exceeds T at these sizes
-    part = _partition(NG, S, sb, nf, H, XL, XU)
-
-    def fast(s):  # bm2's test for the unaligned-dword copy, left pass
-        x0 = (sb + s) * 32
-        PB = x0 - R - m + NC - 1
-        return PB - 4 * NJ4 >= 0 and PB <= W - 1 and x0 - R >= 0 and x0 - R + 4 * NC4 - 1 <= W - 1
-
-    out = []
-    for b in range(NG):
-        it, lin1, segs = part[b], part[b + 1], []
-        while it < lin1:
-            sidx, yb = it // H, it % H
-            ye = min(H, yb + lin1 - it)
-            segs.append((sidx // S, sidx % S, yb, ye - yb, fast(sidx % S)))
-            it += ye - yb
-        out.append(segs)
-    assert sum(s[3] for segs in out for s in segs) == T
-    return out
+    """Per block of a left-pass launch its segments (fused_geometry.Seg), in order."""
+    return fg.blocks(H, gb, W, m, nf, R, d)
 
 
 def _kinds(blocks, H, R=BS // 2):
@@ -123,33 +50,16 @@ def _kinds(blocks, H, R=BS // 2):
     k = set()
     for b in blocks:
         for s in b:
-            p = "f:" if s[4] else "c:"
-            for name, hit in (("row0", s[2] == 0), ("last", s[2] == H - 1), ("last-R", s[2] == H - 1 - R and s[2] > 0),
-                              ("inside", 0 < s[2] < H - 1), ("one", s[3] == 1), ("long", s[3] >= 2 * R + 2)):
+            p = "f:" if s.fast else "c:"
+            for name, hit in (("row0", s.y0 == 0), ("last", s.y0 == H - 1), ("last-R", s.y0 == H - 1 - R and s.y0 > 0),
+                              ("inside", 0 < s.y0 < H - 1), ("one", s.rows == 1), ("long", s.rows >= 2 * R + 2)):
                 if hit:
                     k.add(p + name)
-        if len(b) > 1 and any(p[1] != q[1] and p[0] == q[0] for p, q in zip(b, b[1:])):
+        if len(b) > 1 and any(p.strip != q.strip and p.frame == q.frame for p, q in zip(b, b[1:])):
             k.add("next_strip")
-        if len(b) > 1 and any(p[0] != q[0] for p, q in zip(b, b[1:])):
+        if len(b) > 1 and any(p.frame != q.frame for p, q in zip(b, b[1:])):
             k.add("next_frame")
     return k
-
-
-# ---- comparison --------------------------------------------------------------------------------------
-
-def _check(got, want, what):
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, (f"{what}: {len(bad)} of {got.size} pixels differ, first {bad[:4].tolist()}: "
-                           f"got {got[tuple(bad[0])]} want {want[tuple(bad[0])]}")
-
-
-def _check_maps(fixed, flt, want, what, fmode="fixed"):
-    wf = want["fixed"]
-    _check(fixed.cpu().numpy(), wf, what + " fixed")
-    if fmode == "fixed":
-        _check(flt.cpu().numpy(), wf.astype(np.float32) / np.float32(16), what + " float")
-    else:
-        _check(flt.cpu().numpy().view(np.int32), want["parabola"].view(np.int32), what + " float (parabola, bits)")
 
 
 def _run(torch, dL, dR, shape, want, what, grids, fmode="fixed", **kw):
@@ -161,7 +71,7 @@ def _run(torch, dL, dR, shape, want, what, grids, fmode="fixed", **kw):
             fl = torch.empty(shape, dtype=torch.float32, device="cuda")
             mt.compute_device(dL, dR, out_fixed=fx, out_float=fl)
             torch.cuda.synchronize()
-            _check_maps(fx, fl, want, f"{what} grid_blocks={g}", fmode)
+            fg.check_maps(fx, fl, want, f"{what} grid_blocks={g}", fmode)
         finally:
             mt.close()
 
@@ -173,7 +83,7 @@ def _pair(H, W=W0, m=M, d=D, seed=0):
 
 def _both_modes(torch, key, L, R, grids, what, d=D, bs=BS, u=10, lr=-1, **kw):
     """Both float modes (the int16 map with each)."""
-    want = _want(key, L, R, M, d, bs, u, True, lr)
+    want = fg.want(key, L, R, M, d, bs, u, True, lr)
     dL, dR = torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda()
     par = dict(BASE, num_disp=d, block_size=bs, uniqueness_ratio=u, disp12_max_diff=lr)
     par.update(kw)
@@ -188,7 +98,7 @@ def test_short_frames(torch_dev, H):
     """Frames shorter than, equal to and just above 2R+1 = 9 rows: the init clamps at both ends.  One block per
     strip (every segment starts at row 0 and takes the whole frame) and one per row."""
     whole, rows = _kinds(_blocks(H, 5), H), _kinds(_blocks(H, 0), H)
-    assert {"f:row0", "c:row0"} <= whole and all(len(b) == 1 and b[0][3] == H for b in _blocks(H, 5))
+    assert {"f:row0", "c:row0"} <= whole and all(len(b) == 1 and b[0].rows == H for b in _blocks(H, 5))
     # the strips with clamped bytes weigh more and get a block per row; those with unaligned dwords get one per row
     # only in frames of one or two rows (above that their last segment has two rows or more at every grid)
     assert {"f:one", "c:one", "c:last"} <= rows and (H > 2 or "f:last" in rows)
@@ -216,7 +126,7 @@ def test_segment_starts(torch_dev, H, gb):
     blocks = _blocks(H, gb)
     assert CLAIMS[(H, gb)] <= _kinds(blocks, H), (H, gb, blocks)
     if (H, gb) == (20, 20):  # rows 15..19 of a strip with the unaligned-dword loads are one segment
-        assert any(s[2] == 15 and s[3] == 5 and s[4] for b in blocks for s in b)
+        assert any(s.y0 == 15 and s.rows == 5 and s.fast for b in blocks for s in b)
     L, R = _pair(H)
     _both_modes(torch_dev, ("random", H), L, R, (gb,), f"H={H} random")
     _both_modes(torch_dev, ("random", H), L, R, (gb,), f"H={H} random u=0", u=0)
@@ -264,7 +174,7 @@ def test_batch_of_two_frames(torch_dev):
     assert {"next_frame", "next_strip", "f:row0", "c:last", "f:inside"} <= kinds
     dL = torch.from_numpy(np.stack([f[0] for f in fr])).cuda()
     dR = torch.from_numpy(np.stack([f[1] for f in fr])).cuda()
-    wants = [_want(("random", H) if i == 0 else ("random1", H), L, R, M, D, BS, 10, True) for i, (L, R) in enumerate(fr)]
+    wants = [fg.want(("random", H) if i == 0 else ("random1", H), L, R, M, D, BS, 10, True) for i, (L, R) in enumerate(fr)]
     for g in (0, 3, 7):
         mt = HipBlockMatcher(grid_blocks=g, uniqueness_ratio=10, **BASE)
         try:
@@ -273,7 +183,7 @@ def test_batch_of_two_frames(torch_dev):
             mt.compute_batch_device(dL, dR, out_fixed=fx, out_float=fl)
             torch.cuda.synchronize()
             for i in range(2):
-                _check_maps(fx[i], fl[i], wants[i], f"batch grid_blocks={g} frame={i}")
+                fg.check_maps(fx[i], fl[i], wants[i], f"batch grid_blocks={g} frame={i}")
         finally:
             mt.close()
 
@@ -294,7 +204,7 @@ def test_strided_views(torch_dev, off):
         buf = torch.from_numpy(host).cuda()
         views.append(torch.as_strided(buf, (H, W0), (stride, 1), o))
     assert views[0].data_ptr() % 4 == off and views[0].stride(0) == stride
-    want = _want(("random", H), L, R, M, D, BS, 10, True)
+    want = fg.want(("random", H), L, R, M, D, BS, 10, True)
     _run(torch, views[0], views[1], L.shape, want, f"views off={off}", (10, 0), uniqueness_ratio=10, **BASE)
 
 
@@ -304,7 +214,7 @@ def test_in_flight_handle(torch_dev):
     from depthestimation_amd.matcher import HipBlockMatcher
     H = 20
     L, R = _pair(H)
-    want = _want(("random", H), L, R, M, D, BS, 10, True)
+    want = fg.want(("random", H), L, R, M, D, BS, 10, True)
     dL, dR = torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda()
     assert "f:one" in _kinds(_blocks(H, 0), H)  # the resident capacity exceeds the 100 rows: a block per row
     mt = HipBlockMatcher(in_flight=True, uniqueness_ratio=10, **BASE)
@@ -317,7 +227,7 @@ def test_in_flight_handle(torch_dev):
             mt.compute_device(dL, dR, out_fixed=fx[i], out_float=fl[i], stream=st)
         torch.cuda.synchronize()
         for i in range(2):
-            _check_maps(fx[i], fl[i], want, f"in_flight call {i}")
+            fg.check_maps(fx[i], fl[i], want, f"in_flight call {i}")
     finally:
         mt.close()
 

@@ -9,8 +9,8 @@ column.
 
 Every comparison is bit for bit over all pixels against the C oracle (oracle/cref.py): the int16 x16 map and
 the float map - float mode 'fixed' against x16 / 16 (exact in f32), 'parabola' by bit pattern.  Every case
-asserts from a restatement of the launch geometry (launch_bm2_side and bm2 in csrc/dsx_bm.hip, the host partition
-of csrc/dsx_partition.h) that a strip with the unaligned-dword loads runs, and where the column update matters
+asserts from the launch geometry restated in tests/fused_geometry.py (the plan functions of
+csrc/dsx_partition.h) that a strip with the unaligned-dword loads runs, and where the column update matters
 that one of its segments has two rows or more (a segment's first row has no column update).
 
 Base: D = 128, block 9, W = 256: strips 3..7 run, x0 = 160 and 192 with the unaligned-dword loads.
@@ -21,7 +21,8 @@ import numpy as np
 import pytest
 
 from depthestimation_amd.synthetic import binary_pair, stereo_pair
-from oracle.cref import CRef
+
+import fused_geometry as fg
 
 pytestmark = pytest.mark.gpu
 
@@ -37,107 +38,16 @@ def torch_dev():
     return torch
 
 
-_CREF = []
-_WANT = {}
-
-
-def _want(key, L, R, m, d, bs, u, sp):
-    """Oracle maps, computed once per (input, parameters) and shared by the tests."""
-    k = (key, m, d, bs, u, sp)
-    if k not in _WANT:
-        if not _CREF:
-            _CREF.append(CRef())
-        _WANT[k] = _CREF[0](L, R, m, d, bs, "sad", u, -1, sp)
-    return _WANT[k]
-
-
-# ---- launch geometry, restated -----------------------------------------------------------------------
-
-def _partition(NG, S, sb, nf, H, XL, XU, TX=32, w8=11):
-    """bm2_partition with one age level (every block weighs the same)."""
-    NS = S * nf
-    if NG < NS:
-        return [b * NS * H // NG for b in range(NG + 1)]
-    slo = min(max((XL + TX - 1) // TX - sb, 0), S)
-    shi = min(max(XU // TX - sb + 1, slo), S)
-    if w8 < 8 or NG * 8 < NS * w8 + 8 * NS:
-        w8 = 8
-    ex = w8 - 8
-    Pf = lambda s: 8 * s + ex * (min(s, slo) + max(0, s - shi))  # noqa: E731
-    Uf = Pf(S)
-    U = Uf * nf
-    P = lambda g: (g // S) * Uf + Pf(g % S)  # noqa: E731
-    start, b = [], 0
-    for g in range(NS + 1):
-        while b < NG and b * U < P(g) * NG:
-            b += 1
-        start.append(b)
-    part = [0] * (NG + 1)
-    for g in range(NS):
-        qd = start[g + 1] - start[g]
-        for bb in range(start[g], start[g + 1] + 1):
-            part[bb] = g * H + (bb - start[g]) * H // qd
-    part[NG] = NS * H
-    return part
-
-
-def _fast(x0, W, m, R):
-    """The segment's FAST test of the left pass (Dp = 128): every staged search position and the reference
-    bytes [x0 - R, x0 - R + 4 NC4) lie inside the row."""
-    NC = 32 + 2 * R
-    NJ4, NC4 = (NC + 128 + 3) // 4, (NC + 3) // 4
-    PB = x0 - R - m + NC - 1
-    return PB - 4 * NJ4 >= 0 and PB <= W - 1 and x0 - R >= 0 and x0 - R + 4 * NC4 - 1 <= W - 1
-
-
 def _segments(H, gb, W=W0, m=M, nf=1, bs=BS, d=D):
-    """(frame, x0, first row, rows, FAST) of every segment of a left-pass launch."""
-    R = bs // 2
-    NC = 32 + 2 * R
-    NJ4, NC4 = (NC + 128 + 3) // 4, (NC + 3) // 4
-    xlo, xhi = max(0, m + d - 1), min(W - 1, W - 1 + m)
-    sb = xlo // 32
-    S = xhi // 32 + 1 - sb
-    XL = max(4 * NJ4 + R + m - NC + 1, R)
-    XU = min(W - 1 + R + m - NC + 1, W - 1 + R - 4 * NC4 + 1)
-    T = S * nf * H
-    NG = min(gb, T) if gb > 0 else T  # the resident capacity (thousands of blocks) exceeds T at these sizes
-    part = _partition(NG, S, sb, nf, H, XL, XU)
-    out = []
-    for b in range(NG):
-        it, lin1 = part[b], part[b + 1]
-        while it < lin1:
-            sidx, yb = it // H, it % H
-            ye = min(H, yb + lin1 - it)
-            x0 = 32 * (sb + sidx % S)
-            out.append((sidx // S, x0, yb, ye - yb, _fast(x0, W, m, R)))
-            it += ye - yb
-    assert sum(s[3] for s in out) == T
-    return out
+    """Every segment (fused_geometry.Seg; FAST = its fast flag) of a left-pass launch."""
+    return [s for b in fg.blocks(H, gb, W, m, nf, bs // 2, d) for s in b]
 
 
 def _covered(H, gb, rows=1, **kw):
     """The coverage assertion: a FAST segment of at least ``rows`` rows runs.  Returns the FAST segments."""
-    segs = [s for s in _segments(H, gb, **kw) if s[4]]
-    assert segs and max(s[3] for s in segs) >= rows, (H, gb, kw, segs)
+    segs = [s for s in _segments(H, gb, **kw) if s.fast]
+    assert segs and max(s.rows for s in segs) >= rows, (H, gb, kw, segs)
     return segs
-
-
-# ---- comparison --------------------------------------------------------------------------------------
-
-def _check(got, want, what):
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, (f"{what}: {len(bad)} of {got.size} pixels differ, first {bad[:4].tolist()}: "
-                           f"got {got[tuple(bad[0])]} want {want[tuple(bad[0])]}")
-
-
-def _check_maps(fixed, flt, want, what, fmode="fixed"):
-    wf = want["fixed"]
-    _check(fixed.cpu().numpy(), wf, what + " fixed")
-    if fmode == "fixed":
-        _check(flt.cpu().numpy(), wf.astype(np.float32) / np.float32(16), what + " float")
-    else:
-        _check(flt.cpu().numpy().view(np.int32), want["parabola"].view(np.int32), what + " float (parabola, bits)")
 
 
 def _run(torch, dL, dR, shape, want, what, grids, fmode="fixed", stride=None, **kw):
@@ -150,7 +60,7 @@ def _run(torch, dL, dR, shape, want, what, grids, fmode="fixed", stride=None, **
             fl = torch.empty(shape, dtype=torch.float32, device="cuda")
             mt.compute_device(dL, dR, out_fixed=fx, out_float=fl, stride=stride)
             torch.cuda.synchronize()
-            _check_maps(fx, fl, want, f"{what} grid_blocks={g}", fmode)
+            fg.check_maps(fx, fl, want, f"{what} grid_blocks={g}", fmode)
         finally:
             mt.close()
 
@@ -165,7 +75,7 @@ def _all_modes(torch, key, L, R, grids, what, m=M, d=D, bs=BS, modes=(("fixed", 
     dL, dR = torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda()
     for u in us:
         for fmode, sp in modes:
-            want = _want(key, L, R, m, d, bs, u, sp)
+            want = fg.want(key, L, R, m, d, bs, u, sp)
             _run(torch, dL, dR, L.shape, want, f"{what} u={u} {fmode} subpixel={sp}", grids, fmode=fmode,
                  uniqueness_ratio=u, subpixel=sp, **kw)
 
@@ -175,15 +85,15 @@ def _all_modes(torch, key, L, R, grids, what, m=M, d=D, bs=BS, modes=(("fixed", 
 def test_base_geometry():
     """x0 = 160 and 192 are the FAST strips of the base shape, and the (H, grid_blocks) set of the base test holds
     FAST segments of 1, 2, 3 and 20 or more rows and blocks that run on from a FAST strip into the next one."""
-    assert sorted({s[1] for s in _segments(24, 0) if s[4]}) == [160, 192]
-    assert sorted({s[1] for s in _segments(24, 0) if not s[4]}) == [96, 128, 224]
+    assert sorted({s.x0 for s in _segments(24, 0) if s.fast}) == [160, 192]
+    assert sorted({s.x0 for s in _segments(24, 0) if not s.fast}) == [96, 128, 224]
     lens = set()
     for H in (1, 2, 7, 24):
         for gb in (0, 1, 4):
-            lens |= {s[3] for s in _covered(H, gb)}
+            lens |= {s.rows for s in _covered(H, gb)}
     assert {1, 2, 3} <= lens and max(lens) >= 20, lens
     # one block: strips in a row, the rows taken ahead at the end of x0 = 160 are dropped at the start of x0 = 192
-    assert [(s[1], s[3]) for s in _segments(24, 1)] == [(96, 24), (128, 24), (160, 24), (192, 24), (224, 24)]
+    assert [(s.x0, s.rows) for s in _segments(24, 1)] == [(96, 24), (128, 24), (160, 24), (192, 24), (224, 24)]
 
 
 @pytest.mark.parametrize("H", [1, 2, 7, 24])
@@ -221,7 +131,7 @@ def test_alignment_of_views(torch_dev, off, pad):
     _covered(H, 4, rows=2)
     _covered(H, 1, rows=2)
     L, R = _pair(H)
-    want = _want(("random", H), L, R, M, D, BS, 10, True)
+    want = fg.want(("random", H), L, R, M, D, BS, 10, True)
     (bl, vl), (br, vr) = _views(torch, L, R, off, W0 + pad)
     assert vl.data_ptr() % 4 == (bl.data_ptr() + off) % 4 and vl.stride(0) == W0 + pad
     _run(torch, vl, vr, L.shape, want, f"views off={off} stride=W+{pad}", (4,), uniqueness_ratio=10, **BASE)
@@ -237,14 +147,14 @@ def test_left_image_ends_its_allocation(torch_dev, W):
     being aligned and W a multiple of 4, no further dword is read)."""
     torch = torch_dev
     H = 7
-    fast = sorted({s[1] for s in _covered(H, 4, rows=2, W=W)})
+    fast = sorted({s.x0 for s in _covered(H, 4, rows=2, W=W)})
     assert fast[-1] == (224 if W == 288 else 256)
     assert (fast[-1] - BS // 2 + 40 == W) == (W == 292)
     L, R = _pair(H, W=W, seed=W)
     dL, dR = torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda()
     assert dL.numel() == H * W and dL.is_contiguous()
     for u in (0, 10):
-        want = _want(("random", H, W), L, R, M, D, BS, u, True)
+        want = fg.want(("random", H, W), L, R, M, D, BS, u, True)
         _run(torch, dL, dR, L.shape, want, f"W={W} u={u}", (0, 1, 4), uniqueness_ratio=u, **BASE)
 
 
@@ -261,7 +171,7 @@ def test_block_sizes(torch_dev, bs):
         _all_modes(torch, ("random", H), L, R, (gb,), f"block {bs} H={H}", bs=bs)
     H = 7
     L, R = _pair(H)
-    want = _want(("random", H), L, R, M, D, bs, 10, True)
+    want = fg.want(("random", H), L, R, M, D, bs, 10, True)
     (_, vl), (_, vr) = _views(torch, L, R, 1, W0 + 3)
     _run(torch, vl, vr, L.shape, want, f"block {bs} view off=1 stride=W+3", (4,), uniqueness_ratio=10,
          **dict(BASE, block_size=bs))
@@ -278,7 +188,7 @@ def test_extreme_and_constant_values(torch_dev):
     assert set(np.unique(Lb)) <= {0, 255} and set(np.unique(Rb)) <= {0, 255}
     _all_modes(torch_dev, ("binary", H), Lb, Rb, (0, 1, 4), "binary")
     C = np.full((H, W0), 93, np.uint8)
-    want = _want(("const", H), C, C, M, D, BS, 0, True)
+    want = fg.want(("const", H), C, C, M, D, BS, 0, True)
     assert np.all(want["fixed"][:, D - 1:] == 0)
     _all_modes(torch_dev, ("const", H), C, C.copy(), (0, 1, 4), "constant")
 
@@ -309,7 +219,7 @@ def test_batch_of_two_frames(torch_dev):
     L1, R1 = _pair(H, seed=1)
     fr = [(L0, R0), (L1, R1)]
     for g in (0, 1, 3):
-        assert {s[0] for s in _covered(H, g, nf=2)} == {0, 1}
+        assert {s.frame for s in _covered(H, g, nf=2)} == {0, 1}
     fs = H * W0 + 5
     bufs = []
     for k in range(2):
@@ -318,7 +228,7 @@ def test_batch_of_two_frames(torch_dev):
         v.copy_(torch.from_numpy(np.stack([f[k] for f in fr])).cuda())
         bufs.append((b, v))
     for u in (0, 10):
-        wants = [_want(("random", H) if i == 0 else ("random1", H), L, R, M, D, BS, u, True) for i, (L, R) in enumerate(fr)]
+        wants = [fg.want(("random", H) if i == 0 else ("random1", H), L, R, M, D, BS, u, True) for i, (L, R) in enumerate(fr)]
         for g in (0, 1, 3):
             mt = HipBlockMatcher(grid_blocks=g, uniqueness_ratio=u, **BASE)
             try:
@@ -327,7 +237,7 @@ def test_batch_of_two_frames(torch_dev):
                 mt.compute_batch_device(bufs[0][1], bufs[1][1], out_fixed=fx, out_float=fl)
                 torch.cuda.synchronize()
                 for i in range(2):
-                    _check_maps(fx[i], fl[i], wants[i], f"batch u={u} grid_blocks={g} frame={i}")
+                    fg.check_maps(fx[i], fl[i], wants[i], f"batch u={u} grid_blocks={g} frame={i}")
             finally:
                 mt.close()
 
@@ -339,7 +249,7 @@ def test_in_flight_handles(torch_dev):
     H = 24
     _covered(H, 0, rows=1)
     fr = [_pair(H), binary_pair(H, W0, M, D, seed=191 + H)[:2]]
-    wants = [_want(("random", H), *fr[0], M, D, BS, 0, True), _want(("binary", H), *fr[1], M, D, BS, 0, True)]
+    wants = [fg.want(("random", H), *fr[0], M, D, BS, 0, True), fg.want(("binary", H), *fr[1], M, D, BS, 0, True)]
     dev = [(torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda()) for L, R in fr]
     handles = [HipBlockMatcher(in_flight=True, uniqueness_ratio=0, **BASE) for _ in range(2)]
     streams = [torch.cuda.Stream() for _ in range(2)]
@@ -351,7 +261,7 @@ def test_in_flight_handles(torch_dev):
             handles[i % 2].compute_device(*dev[i % 2], out_fixed=fx[i], out_float=fl[i], stream=streams[i % 2])
         torch.cuda.synchronize()
         for i in range(4):
-            _check_maps(fx[i], fl[i], wants[i % 2], f"in_flight handle {i % 2} call {i // 2}")
+            fg.check_maps(fx[i], fl[i], wants[i % 2], f"in_flight handle {i % 2} call {i // 2}")
     finally:
         for h in handles:
             h.close()
@@ -365,9 +275,9 @@ def test_in_flight_grid_below_the_row_count(torch_dev):
     torch = torch_dev
     from depthestimation_amd.matcher import HipBlockMatcher
     H = 480
-    assert {s[3] for s in _covered(H, 2048, rows=2)} == {1, 2}
+    assert {s.rows for s in _covered(H, 2048, rows=2)} == {1, 2}
     L, R = _pair(H)
-    want = _want(("random", H), L, R, M, D, BS, 10, True)
+    want = fg.want(("random", H), L, R, M, D, BS, 10, True)
     dL, dR = torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda()
     for fl in (True, False):
         mt = HipBlockMatcher(in_flight=fl, uniqueness_ratio=10, **BASE)
@@ -376,7 +286,7 @@ def test_in_flight_grid_below_the_row_count(torch_dev):
             fo = torch.empty(L.shape, dtype=torch.float32, device="cuda")
             mt.compute_device(dL, dR, out_fixed=fx, out_float=fo)
             torch.cuda.synchronize()
-            _check_maps(fx, fo, want, f"H={H} in_flight={fl}")
+            fg.check_maps(fx, fo, want, f"H={H} in_flight={fl}")
         finally:
             mt.close()
 
@@ -396,11 +306,11 @@ def test_rows_written_by_the_prefilter(torch_dev):
     mt = HipBlockMatcher(grid_blocks=4, uniqueness_ratio=10, prefilter_type="xsobel", prefilter_cap=31, **BASE)
     try:
         for i, (L, R) in enumerate(frames):
-            want = _want(("xsobel", H, i), prefilter_xsobel(L, 31), prefilter_xsobel(R, 31), M, D, BS, 10, True)
+            want = fg.want(("xsobel", H, i), prefilter_xsobel(L, 31), prefilter_xsobel(R, 31), M, D, BS, 10, True)
             fx = torch.empty(L.shape, dtype=torch.int16, device="cuda")
             fl = torch.empty(L.shape, dtype=torch.float32, device="cuda")
             mt.compute_device(torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda(), out_fixed=fx, out_float=fl)
             torch.cuda.synchronize()
-            _check_maps(fx, fl, want, f"xsobel frame {i}")
+            fg.check_maps(fx, fl, want, f"xsobel frame {i}")
     finally:
         mt.close()

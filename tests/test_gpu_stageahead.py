@@ -11,9 +11,9 @@ flips once per step), a slot written while its last reader still needs it, an ou
 row or held across a step that has none, and the places the staging stands in: a one-step segment stages nothing
 that is used, a two-step segment uses the first staged slots exactly once, and from three steps on a step reads what
 the step before staged.  So the cases are chosen by segment length, first-row parity and position
-in the frame, from a restatement of the host partition (csrc/dsx_partition.h, equal block weights) and of the
-kernel's test for the unaligned-dword copy ("f:" below; the others, "c:", take clamped bytes), and every case asserts
-from that restatement that the classes it is there for occur.
+in the frame, from the launch geometry restated in tests/fused_geometry.py (the host partition and the kernel's
+test for the unaligned-dword copy, "f:" below; the others, "c:", take clamped bytes), and every case asserts from
+that restatement that the classes it is there for occur.
 
 Every comparison is bit for bit over all pixels against the C oracle (oracle/cref.py): the int16 x16 map and the
 float map - float mode 'fixed' against x16 / 16 (exact in f32), 'parabola' by bit pattern.
@@ -27,7 +27,8 @@ import numpy as np
 import pytest
 
 from depthestimation_amd.synthetic import stereo_pair
-from oracle.cref import CRef
+
+import fused_geometry as fg
 
 pytestmark = pytest.mark.gpu
 
@@ -43,83 +44,9 @@ def torch_dev():
     return torch
 
 
-_CREF = []
-_WANT = {}
-
-
-def _want(key, L, R, m, d, bs, u, sp, lr=-1):
-    """Oracle maps, computed once per (input, parameters) and shared by the tests."""
-    k = (key, m, d, bs, u, sp, lr)
-    if k not in _WANT:
-        if not _CREF:
-            _CREF.append(CRef())
-        _WANT[k] = _CREF[0](L, R, m, d, bs, "sad", u, lr, sp)
-    return _WANT[k]
-
-
-# ---- host partition, restated (bm2_partition with one age level: every block weighs the same) --------
-
-def _partition(NG, S, sb, nf, H, XL, XU, TX=32, w8=11):
-    NS = S * nf
-    if NG < NS:
-        return [b * NS * H // NG for b in range(NG + 1)]
-    slo = min(max((XL + TX - 1) // TX - sb, 0), S)
-    shi = min(max(XU // TX - sb + 1, slo), S)
-    if w8 < 8 or NG * 8 < NS * w8 + 8 * NS:
-        w8 = 8
-    ex = w8 - 8
-    Pf = lambda s: 8 * s + ex * (min(s, slo) + max(0, s - shi))  # noqa: E731
-    Uf = Pf(S)
-    U = Uf * nf
-    P = lambda g: (g // S) * Uf + Pf(g % S)  # noqa: E731
-    start, b = [], 0
-    for g in range(NS + 1):
-        while b < NG and b * U < P(g) * NG:
-            b += 1
-        start.append(b)
-    part = [0] * (NG + 1)
-    for g in range(NS):
-        qd = start[g + 1] - start[g]
-        for bb in range(start[g], start[g + 1] + 1):
-            part[bb] = g * H + (bb - start[g]) * H // qd
-    part[NG] = NS * H
-    return part
-
-
-def _dp(d):
-    """Disparities per block: SAD1 (one per lane) up to 64, else pairs in one, two or four waves."""
-    return 64 if d <= 64 else (128 if d <= 128 else (256 if d <= 256 else 512))
-
-
 def _blocks(H, gb, W=W0, m=M, nf=1, R=BS // 2, d=D):
-    """Per block of a left-pass launch its segments (frame, strip, first row, row count, fast), in order."""
-    NC, Dp = 32 + 2 * R, _dp(d)
-    NJ4, NC4 = (NC + Dp + 3) // 4, (NC + 3) // 4
-    xlo, xhi = max(0, m + d - 1), min(W - 1, W - 1 + m)
-    sb = xlo // 32
-    S = xhi // 32 + 1 - sb
-    XL = max(4 * NJ4 + R + m - NC + 1, R)
-    XU = min(W - 1 + R + m - NC + 1, W - 1 + R - 4 * NC4 + 1)
-    T = S * nf * H
-    NG = min(gb, T) if gb > 0 else T  # the resident capacity (thousands of blocks) exceeds T at these sizes
-    part = _partition(NG, S, sb, nf, H, XL, XU)
-
-    def fast(s):  # bm2's test for the unaligned-dword copy, left pass
-        x0 = (sb + s) * 32
-        PB = x0 - R - m + NC - 1
-        return PB - 4 * NJ4 >= 0 and PB <= W - 1 and x0 - R >= 0 and x0 - R + 4 * NC4 - 1 <= W - 1
-
-    out = []
-    for b in range(NG):
-        it, lin1, segs = part[b], part[b + 1], []
-        while it < lin1:
-            sidx, yb = it // H, it % H
-            ye = min(H, yb + lin1 - it)
-            segs.append((sidx // S, sidx % S, yb, ye - yb, fast(sidx % S)))
-            it += ye - yb
-        out.append(segs)
-    assert sum(s[3] for segs in out for s in segs) == T
-    return out
+    """Per block of a left-pass launch its segments (fused_geometry.Seg), in order."""
+    return fg.blocks(H, gb, W, m, nf, R, d)
 
 
 def _kinds(blocks, H):
@@ -132,39 +59,22 @@ def _kinds(blocks, H):
     k = set()
     for b in blocks:
         for s in b:
-            p = "f:" if s[4] else "c:"
-            n = s[3]
+            p = "f:" if s.fast else "c:"
+            n = s.rows
             k.add(p + ("n4+" if n >= 4 else f"n{n}"))
             if n >= 2:
-                k.add(p + ("odd" if s[2] & 1 else "even"))
-                if s[2] == 0:
+                k.add(p + ("odd" if s.y0 & 1 else "even"))
+                if s.y0 == 0:
                     k.add(p + "row0")
-                if s[2] + n == H:
+                if s.y0 + n == H:
                     k.add(p + "last")
         for p, q in zip(b, b[1:]):
-            if p[0] == q[0] and q[1] == p[1] + 1 and p[2] + p[3] == H and q[2] == 0:
+            if p.frame == q.frame and q.strip == p.strip + 1 and p.y0 + p.rows == H and q.y0 == 0:
                 k.add("next_strip")
     for b, c in zip(blocks, blocks[1:]):
-        if b and c and c[0][0] == b[-1][0] + 1 and c[0][1] == 0 and c[0][2] == 0 and b[-1][2] + b[-1][3] == H:
+        if b and c and c[0].frame == b[-1].frame + 1 and c[0].strip == 0 and c[0].y0 == 0 and b[-1].y0 + b[-1].rows == H:
             k.add("frame_cut")
     return k
-
-
-# ---- comparison --------------------------------------------------------------------------------------
-
-def _check(got, want, what):
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, (f"{what}: {len(bad)} of {got.size} pixels differ, first {bad[:4].tolist()}: "
-                           f"got {got[tuple(bad[0])]} want {want[tuple(bad[0])]}")
-
-
-def _check_maps(fixed, flt, want, what, fmode="fixed"):
-    wf = want["fixed"]
-    _check(fixed.cpu().numpy(), wf, what + " fixed")
-    if fmode == "fixed":
-        _check(flt.cpu().numpy(), wf.astype(np.float32) / np.float32(16), what + " float")
-    else:
-        _check(flt.cpu().numpy().view(np.int32), want["parabola"].view(np.int32), what + " float (parabola, bits)")
 
 
 def _run(torch, dL, dR, shape, want, what, grids, fmode="fixed", **kw):
@@ -176,7 +86,7 @@ def _run(torch, dL, dR, shape, want, what, grids, fmode="fixed", **kw):
             fl = torch.empty(shape, dtype=torch.float32, device="cuda")
             mt.compute_device(dL, dR, out_fixed=fx, out_float=fl)
             torch.cuda.synchronize()
-            _check_maps(fx, fl, want, f"{what} grid_blocks={g}", fmode)
+            fg.check_maps(fx, fl, want, f"{what} grid_blocks={g}", fmode)
         finally:
             mt.close()
 
@@ -188,7 +98,7 @@ def _pair(H, W=W0, m=M, d=D, seed=0):
 
 def _both_modes(torch, key, L, R, grids, what, d=D, bs=BS, u=10, lr=-1, **kw):
     """Both float modes (the int16 map with each)."""
-    want = _want(key, L, R, M, d, bs, u, True, lr)
+    want = fg.want(key, L, R, M, d, bs, u, True, lr)
     dL, dR = torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda()
     par = dict(BASE, num_disp=d, block_size=bs, uniqueness_ratio=u, disp12_max_diff=lr)
     par.update(kw)
@@ -223,7 +133,7 @@ def test_segment_lengths(torch_dev, H, gb):
     blocks = _blocks(H, gb)
     assert CLAIMS[(H, gb)] <= _kinds(blocks, H), (H, gb, sorted(_kinds(blocks, H)), blocks)
     if (H, gb) == (12, 0):  # no segment of the clamped strips has a second step
-        assert all(s[3] == 1 for b in blocks for s in b if not s[4])
+        assert all(s.rows == 1 for b in blocks for s in b if not s.fast)
     L, R = _pair(H)
     _both_modes(torch_dev, ("random", H), L, R, (gb,), f"H={H} random")
     _both_modes(torch_dev, ("random", H), L, R, (gb,), f"H={H} random u=0", u=0)
@@ -269,7 +179,7 @@ def test_no_subpixel(torch_dev):
     H, gb = 13, 20
     assert {"f:n3", "c:n3", "f:odd"} <= _kinds(_blocks(H, gb), H)
     L, R = _pair(H)
-    want = _want(("random", H), L, R, M, D, BS, 10, False)
+    want = fg.want(("random", H), L, R, M, D, BS, 10, False)
     dL, dR = torch_dev.from_numpy(L).cuda(), torch_dev.from_numpy(R).cuda()
     _run(torch_dev, dL, dR, L.shape, want, "subpixel off", (gb,), uniqueness_ratio=10, subpixel=False, **BASE)
 
@@ -306,10 +216,10 @@ def test_batch_of_two_frames(torch_dev):
     grids = (20, 40, 3)
     k20, k40, k3 = (_kinds(_blocks(H, g, nf=2), H) for g in grids)
     assert "frame_cut" in k20 and "f:n4+" in k20 and {"frame_cut", "f:n3", "c:n3"} <= k40 and "next_strip" in k3
-    assert any(len({s[0] for s in b}) == 2 for b in _blocks(H, 3, nf=2))  # a block with rows of both frames
+    assert any(len({s.frame for s in b}) == 2 for b in _blocks(H, 3, nf=2))  # a block with rows of both frames
     dL = torch.from_numpy(np.stack([f[0] for f in fr])).cuda()
     dR = torch.from_numpy(np.stack([f[1] for f in fr])).cuda()
-    wants = [_want(("random", H) if i == 0 else ("random1", H), L, R, M, D, BS, 10, True) for i, (L, R) in enumerate(fr)]
+    wants = [fg.want(("random", H) if i == 0 else ("random1", H), L, R, M, D, BS, 10, True) for i, (L, R) in enumerate(fr)]
     for g in grids:
         mt = HipBlockMatcher(grid_blocks=g, uniqueness_ratio=10, **BASE)
         try:
@@ -318,7 +228,7 @@ def test_batch_of_two_frames(torch_dev):
             mt.compute_batch_device(dL, dR, out_fixed=fx, out_float=fl)
             torch.cuda.synchronize()
             for i in range(2):
-                _check_maps(fx[i], fl[i], wants[i], f"batch grid_blocks={g} frame={i}")
+                fg.check_maps(fx[i], fl[i], wants[i], f"batch grid_blocks={g} frame={i}")
         finally:
             mt.close()
 
@@ -333,7 +243,7 @@ def test_three_handles_in_flight(torch_dev):
     assert "f:n2" in _kinds(_blocks(H, 30), H) and "f:n3" in _kinds(_blocks(H, 20), H) and "next_strip" in _kinds(_blocks(H, 3), H)
     fr = [_pair(H, seed=s) for s in range(NF)]
     keys = [("random", H), ("random1", H), ("random2", H), ("random3", H)]
-    wants = [_want(k, L, R, M, D, BS, 10, True) for k, (L, R) in zip(keys, fr)]
+    wants = [fg.want(k, L, R, M, D, BS, 10, True) for k, (L, R) in zip(keys, fr)]
     dev = [(torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda()) for L, R in fr]
     mts = [HipBlockMatcher(in_flight=True, grid_blocks=g, uniqueness_ratio=10, **BASE) for g in grids]
     sts = [torch.cuda.Stream() for _ in grids]
@@ -347,7 +257,7 @@ def test_three_handles_in_flight(torch_dev):
         torch.cuda.synchronize()
         for h in range(len(grids)):
             for i in range(NF):
-                _check_maps(fx[h][i], fl[h][i], wants[i], f"handle {h} (grid_blocks={grids[h]}) frame {i}")
+                fg.check_maps(fx[h][i], fl[h][i], wants[i], f"handle {h} (grid_blocks={grids[h]}) frame {i}")
     finally:
         for mt in mts:
             mt.close()
