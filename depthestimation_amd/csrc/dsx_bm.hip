@@ -51,6 +51,8 @@ constexpr int kWpeSsd = 4;  // SSD blocks of >= 4 waves
 //   DSX_ROWSTEP_MERGE     merged row staging, one load and one 16-B store per staged row (MRG)
 //   DSX_ROWSTEP_COLGROUP  3-column group sums of the 9x9 and 3x3 rotated loops (CG; DESIGN 4.1,
 //                         profiles/colgroup_isa.txt)
+//   DSX_ROWSTEP_TAILSPLIT rotated loop's tail: both lanes of a pixel key half of the winning block (TSP; DESIGN 4.1,
+//                         profiles/tailsplit_isa.txt)
 //   DSX_SEGSTART_AHEAD    transposed init: chunk q + 1's LDS reads in front of chunk q's SADs (IAH)
 //   DSX_SEGSTART_BATCH    transposed init: every row's loads in one batch ahead of the transposes (IBT)
 // Removed, last present in commit 70ab923 (measurements: DESIGN 4.4, profiles/*_ab.txt): the rejected forms
@@ -68,6 +70,9 @@ constexpr int kWpeSsd = 4;  // SSD blocks of >= 4 waves
 #ifndef DSX_ROWSTEP_COLGROUP
 #define DSX_ROWSTEP_COLGROUP 1
 #endif
+#ifndef DSX_ROWSTEP_TAILSPLIT
+#define DSX_ROWSTEP_TAILSPLIT 1
+#endif
 #ifndef DSX_SEGSTART_AHEAD
 #define DSX_SEGSTART_AHEAD 1
 #endif
@@ -78,6 +83,7 @@ constexpr bool kRowstepAtid = DSX_ROWSTEP_ATID;
 constexpr bool kRowstepKey2 = DSX_ROWSTEP_KEY2;
 constexpr bool kRowstepMerge = DSX_ROWSTEP_MERGE;
 constexpr bool kRowstepColgroup = DSX_ROWSTEP_COLGROUP;
+constexpr bool kRowstepTailsplit = DSX_ROWSTEP_TAILSPLIT;
 constexpr bool kSegstartAhead = DSX_SEGSTART_AHEAD;
 constexpr bool kSegstartBatch = DSX_SEGSTART_BATCH;
 
@@ -883,6 +889,14 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
     static_assert(NQ >= NRS + 2, "a column chunk per stage up to the element keys");
     const int ek = tid / TPP, eh = tid % TPP, ex = x0 + ek;
     const uint8_t *epx = tile + ek * PITCH + eh * DSL * CB;
+    // TSP: the winning block is read and keyed by both lanes of its pixel, four elements each.  The pair-combined
+    // block key names the block for both, so lane eh reads the 8 bytes at 16 egblk + 8 eh of the pixel's tile row
+    // (inside the row for egblk <= 15), forms four element keys (cost << 16 | element 0 .. 3), ors its half's
+    // 4 eh into the free bit 2 and the pair's minimum carries the element 0 .. 7: lowest cost, then lowest element,
+    // as before.  The lane that does not own the block keys no block that cannot win, and the owner select goes.
+    constexpr bool TSP = kRowstepTailsplit && OVL;
+    const uint8_t *ehx = tile + ek * PITCH + 8 * eh;
+    const uint32_t eh4 = (uint32_t)(eh << 2);
     uint4 etv[2] = {};
     uint32_t ekmin = 0, ecb = 0, egblk = 0, ecm = 0, ecp = 0;
     int eb = 0, ef = 0, eden = 1;
@@ -919,18 +933,31 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
                 const uint32_t kmin = gmin<TPP>(ekmin | (uint32_t)(eh * 8));
                 ecb = kmin >> GB;
                 egblk = kmin & ((1u << GB) - 1u);
-                etv[0] = *reinterpret_cast<const uint4 *>(epx + 16 * (egblk & 7u));
+                if constexpr (TSP) {  // this lane's half of the pair's winning block
+                    const uint2 v = *reinterpret_cast<const uint2 *>(ehx + 16 * egblk);
+                    etv[0].x = v.x;
+                    etv[0].y = v.y;
+                } else {
+                    etv[0] = *reinterpret_cast<const uint4 *>(epx + 16 * (egblk & 7u));
+                }
             }
         } else if constexpr (s == NRS + 1) {  // element keys, the winner, its neighbours' reads
-            const uint32_t w4[4] = {etv[0].x, etv[0].y, etv[0].z, etv[0].w};
-            uint32_t k8 = 0xFFFFFFFFu;
+            if constexpr (TSP) {
+                const uint32_t w0 = etv[0].x, w1 = etv[0].y;
+                const uint32_t k4 = umin2(umin2(w0 << 16, (w0 & 0xFFFF0000u) | 1u),
+                                          umin2((w1 << 16) | 2u, (w1 & 0xFFFF0000u) | 3u));
+                eb = (int)(egblk * 8 + (gmin<TPP>(k4 | eh4) & 7u));
+            } else {  // the owner lane keys all eight elements of its block
+                const uint32_t w4[4] = {etv[0].x, etv[0].y, etv[0].z, etv[0].w};
+                uint32_t k8 = 0xFFFFFFFFu;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                k8 = umin2(k8, (w4[q] << 16) | (uint32_t)(2 * q));
-                k8 = umin2(k8, (w4[q] & 0xFFFF0000u) | (uint32_t)(2 * q + 1));
+                for (int q = 0; q < 4; ++q) {
+                    k8 = umin2(k8, (w4[q] << 16) | (uint32_t)(2 * q));
+                    k8 = umin2(k8, (w4[q] & 0xFFFF0000u) | (uint32_t)(2 * q + 1));
+                }
+                const uint32_t dl = (int)(egblk / 8) == eh ? egblk * 8 + (k8 & 7u) : 0xFFFFu;
+                eb = (int)gmin<TPP>(dl);
             }
-            const uint32_t dl = (int)(egblk / 8) == eh ? egblk * 8 + (k8 & 7u) : 0xFFFFu;
-            eb = (int)gmin<TPP>(dl);
             // b - 1 >= -1 and b + 1 <= Dp stay inside the block's LDS: the slot bytes before the tile, the row's padding
             const uint16_t *pc = reinterpret_cast<const uint16_t *>(tile + ek * PITCH) + eb;
             ecm = pc[-1];
