@@ -51,6 +51,7 @@ EXPORTS = (
     "dsx_tfilter_set_params", "dsx_tfilter_reset", "dsx_tfilter_bytes", "dsx_tfilter_destroy",
     "dsx_tfilter_run_device",
     "dsx_default_upsample", "dsx_check_upsample", "dsx_upsample_taps", "dsx_upsample_x0", "dsx_upsample_device",
+    "dsx_block_min8_device",
 )
 
 
@@ -269,6 +270,7 @@ def _bind(lib):
         "dsx_prefilter_device": (ctypes.c_int, [vp, i32, i32, i64, F, vp, i64, vp]),
         "dsx_texture_sum_device": (ctypes.c_int, [vp, i32, i32, i64, i32, i32, vp, vp]),
         "dsx_census_device": (ctypes.c_int, [vp, i32, i32, i64, i32, vp, vp]),
+        "dsx_block_min8_device": (ctypes.c_int, [vp, i64, vp, vp]),
         "dsx_version": (ctypes.c_int, []),
         "dsx_device_count": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)]),
         "dsx_default_params": (None, [P]),

@@ -397,8 +397,11 @@ void set_strips(dsx::Bm2Args &a, const dsx_handle *h, bool band_only) {
     a.strip_count = s.count;
 }
 
-dsx::Bm2Args base_args(dsx_handle *h, int H, int W, int64_t stride, const DsxEnv &env = dsx_env()) {
+// side: the pass (dsx::Side); sg_keys: the left pass takes OpenCV-form LR keys (the caller sets the pointer)
+dsx::Bm2Args base_args(dsx_handle *h, int H, int W, int64_t stride, int side, bool sg_keys = false,
+                       const DsxEnv &env = dsx_env()) {
     dsx::Bm2Args a{};
+    a.side = side;
     a.stride = stride;
     a.H = H;
     a.W = W;
@@ -409,6 +412,8 @@ dsx::Bm2Args base_args(dsx_handle *h, int H, int W, int64_t stride, const DsxEnv
     a.subpix = h->p.subpixel;
     a.float_mode = h->p.float_mode;
     a.padv = pad_value(h, h->g.DB);
+    // the plain left pass up to R = 5 takes block minima as f16 bit patterns: finite padding (dsx_internal.h)
+    if (dsx::bm2_blockmin(h->p.block_size / 2, h->g.kind, h->g.NW, side, sg_keys)) a.padv = dsx::kBlockminPad;
     set_strips(a, h, false);
     a.grid_override = h->p.grid_blocks;
     {
@@ -532,8 +537,7 @@ int run_right_pass(dsx_handle *h, const dsx::CallPlan &pl, const void *dL, const
     ScratchRecord rec_(h, st, pl.scratch);
     int64_t fs = 0;
     if (pl.prefilter && (rc = run_prefilter(h, dL, dR, H, W, stride, st, 1, fs))) return rc;
-    dsx::Bm2Args a = base_args(h, H, W, stride);
-    a.side = dsx::SIDE_RIGHT;
+    dsx::Bm2Args a = base_args(h, H, W, stride, dsx::SIDE_RIGHT);
     a.ref = static_cast<const uint8_t *>(dR);
     a.src = static_cast<const uint8_t *>(dL);
     a.out_dR = out;
@@ -583,8 +587,9 @@ int run_fused(const Call &c) {
     dsx_handle *h = c.h;
     const int H = c.H, W = c.W, nframes = c.pl.nframes, lr = c.pl.lr;
     const DsxEnv env = dsx_env();
-    dsx::Bm2Args a = base_args(h, H, W, c.stride, env);
-    a.side = dsx::SIDE_LEFT;
+    // bm: every strip (below), the LR build of the left pass
+    const int side = lr == dsx::LR_BM ? dsx::SIDE_LEFT_LR : dsx::SIDE_LEFT;
+    dsx::Bm2Args a = base_args(h, H, W, c.stride, side, lr == dsx::LR_SGBM, env);
     a.ref = static_cast<const uint8_t *>(c.dL);
     a.src = static_cast<const uint8_t *>(c.dR);
     a.out_fixed = static_cast<int16_t *>(c.outFixed);
@@ -604,12 +609,9 @@ int run_fused(const Call &c) {
         a.dstar = h->dStar.as<int16_t>();
         a.kshift = h->g.kind != dsx::BM_SAD ? h->g.DB : 16;  // u32 layouts: (C << DB) | d
     }
-    if (lr == dsx::LR_BM) {
-        // every strip: a right pixel's diagonal starts left of the valid band
-        a.side = dsx::SIDE_LEFT_LR;
-    } else {
-        set_strips(a, h, true);  // only strips meeting the valid band need a search
-    }
+    // bm: every strip, a right pixel's diagonal starts left of the valid band; otherwise only strips meeting the
+    // valid band need a search
+    if (lr != dsx::LR_BM) set_strips(a, h, true);
     uint64_t *tl = nullptr;
     const char *tlpath = env.timeline;
     if (tlpath && *tlpath) DSX_HIP(hipMalloc(&tl, 12 * 8 * 65536));
@@ -694,8 +696,7 @@ int build_volume(const Call &c, int f) {
         v.seg = census_seg();
         DSX_LAUNCH(h, "census_volume", c.st, dsx::launch_census_volume(v, c.st));
     } else {  // SAD / SSD block costs: bm2's volume side
-        dsx::Bm2Args a = base_args(h, H, W, c.stride);
-        a.side = dsx::SIDE_VOLUME;
+        dsx::Bm2Args a = base_args(h, H, W, c.stride, dsx::SIDE_VOLUME);
         a.ref = l;
         a.src = r;
         a.vol = h->vol.ptr;
@@ -1124,6 +1125,23 @@ int dsx_census_device(const void *d_img, int32_t H, int32_t W, int64_t stride_by
     c.window = cost;
     c.out64 = 1;
     DSX_HIP(dsx::launch_census_transform(c, static_cast<hipStream_t>(hip_stream)));
+    return DSX_OK;
+}
+
+namespace {
+__global__ __launch_bounds__(256) void block_min8_kernel(const uint4 *blocks, int64_t n, uint32_t *out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = dsx::block_min8<true>(blocks[i]);
+}
+}  // namespace
+
+int dsx_block_min8_device(const void *d_blocks, int64_t n, void *d_out_u32, void *hip_stream) {
+    g_err.clear();
+    if (!d_blocks || !d_out_u32) return fail(DSX_EINVAL, "NULL blocks or output");
+    if (n < 1 || n > (int64_t)1 << 30) return fail(DSX_EINVAL, "n must be in [1, 2^30]");
+    hipLaunchKernelGGL(block_min8_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(hip_stream),
+                       static_cast<const uint4 *>(d_blocks), n, static_cast<uint32_t *>(d_out_u32));
+    DSX_HIP(hipGetLastError());
     return DSX_OK;
 }
 

@@ -53,6 +53,9 @@ constexpr int kWpeSsd = 4;  // SSD blocks of >= 4 waves
 //                         profiles/colgroup_isa.txt)
 //   DSX_ROWSTEP_TAILSPLIT rotated loop's tail: both lanes of a pixel key half of the winning block (TSP; DESIGN 4.1,
 //                         profiles/tailsplit_isa.txt)
+//   DSX_ROWSTEP_BLOCKMIN  rotated loop's block keys: a block's minimum in two packed ops, v_pk_minimum3_f16 and
+//                         v_pk_min_u16 (BMN; DESIGN 4.1, profiles/blockmin_isa.txt).  Declared in dsx_internal.h:
+//                         the host's padding value goes with it
 //   DSX_SEGSTART_AHEAD    transposed init: chunk q + 1's LDS reads in front of chunk q's SADs (IAH)
 //   DSX_SEGSTART_BATCH    transposed init: every row's loads in one batch ahead of the transposes (IBT)
 // Removed, last present in commit 70ab923 (measurements: DESIGN 4.4, profiles/*_ab.txt): the rejected forms
@@ -882,8 +885,15 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
     float e_pf = 0.0f;
     static_assert(!CG || OVL, "group sums: the rotated loop");
     constexpr int CQ = 4, NQ = (NCU + CQ - 1) / CQ;
+    // BMN: a block's minimum (emin8 below) in two packed ops instead of three, v_pk_minimum3_f16 of three of its words
+    // and one v_pk_min_u16 with the fourth (block_min8, dsx_internal.h): every cost of these kernels, the padding
+    // included (the host's kBlockminPad), is below 0x7C00.  The keys are folded as before: hipcc already takes the
+    // running key and two block keys in one v_min3_u32.
+    constexpr bool BMN = kRowstepBlockmin && OVL;
+    static_assert(!BMN || 255 * (2 * R + 1) * (2 * R + 1) < 0x7C00, "block minima as f16 bit patterns: finite costs only");
     // Tile reads per stage and read stages: one read (4 VGPRs in flight) where the chunks suffice, two otherwise.
-    // With two, R = 4 and R = 5 spilled 8 B; four overran the 168 VGPRs even without the reads ahead.
+    // With two, R = 4 and R = 5 spilled 8 B (again with BMN); four overran the 168 VGPRs even without
+    // the reads ahead.
     // Stages 0 .. NRS - 1 read, NRS block keys, NRS + 1 element keys, NRS + 2 sub-pixel step, NRS + 3 outputs.
     constexpr int RPS = NQ >= 10 ? 1 : 2, NRS = 8 / RPS;
     static_assert(NQ >= NRS + 2, "a column chunk per stage up to the element keys");
@@ -901,11 +911,7 @@ __device__ __forceinline__ void bm2_segment(const Bm2Args &a_in, uint8_t *smem, 
     uint32_t ekmin = 0, ecb = 0, egblk = 0, ecm = 0, ecp = 0;
     int eb = 0, ef = 0, eden = 1;
     bool esp = false;
-    auto emin8 = [](uint4 v) __attribute__((always_inline)) -> uint32_t {
-        const u16x2 mm = __builtin_elementwise_min(__builtin_elementwise_min(as2(v.x), as2(v.y)),
-                                                   __builtin_elementwise_min(as2(v.z), as2(v.w)));
-        return umin2(mm.x, mm.y);
-    };
+    auto emin8 = [](uint4 v) __attribute__((always_inline)) -> uint32_t { return block_min8<BMN>(v); };
     // the two output stores of a row, apart from the stage that forms the outputs where that stage defers them
     // ea: the row loop's own copy of the launch arguments.  Taken from the segment's copy (a) the same values come
     // out as another instruction stream (tools/isa_same.py: bm2<R, SAD, 1, 0>, R <= 5).
@@ -1848,6 +1854,8 @@ static hipError_t launch_bm2_side(const Bm2Args &a, hipStream_t st) {
     if (verbose)
         fprintf(stderr, "[dsx] bm2<R=%d,SSD=%d,NW=%d,SIDE=%d> grid %ld (%d/CU) smem %d\n", R, (int)SSD, NW, SIDE, grid,
                 blocks_per_cu[dev], SM);
+    // the float block minima take finite f16 patterns: a host built without the switch would pad with a NaN pattern
+    if (bm2_blockmin(R, SSD ? BM_SSD : (ABS ? BM_SAD1 : BM_SAD), NW, SIDE, false) && a.padv > kBlockminPad) return hipErrorInvalidValue;
     Bm2Args la = a;
     la.nlev = plan.nlev;
     {

@@ -11,6 +11,20 @@ enum Side : int { SIDE_LEFT = 0, SIDE_RIGHT = 1, SIDE_VOLUME = 2, SIDE_LEFT_LR =
 
 constexpr int kVolThreads = 256;    // K2 (volume WTA) block size
 
+// DSX_ROWSTEP_BLOCKMIN (=1 by default; =0 restores the previous form): the rotated row loop of bm2<R, SAD, 1, 0>,
+// R <= 5, takes a tile block's minimum with v_pk_minimum3_f16 (block_min8 below; dsx_bm.hip).
+// Declared here because the host's padding value goes with it: those costs are compared as f16 bit patterns, so the
+// padding is the largest finite one instead of 0xFFFF (a NaN pattern).
+#ifndef DSX_ROWSTEP_BLOCKMIN
+#define DSX_ROWSTEP_BLOCKMIN 1
+#endif
+constexpr bool kRowstepBlockmin = DSX_ROWSTEP_BLOCKMIN;
+constexpr uint32_t kBlockminPad = 0x7BFFu;  // 31,743 > 255 * 11 * 11 = 30,855, the largest cost of those kernels
+// a launch of one of those kernels (side and sg_keys as launch_bm2_one reads them)
+constexpr bool bm2_blockmin(int radius, int kind, int nw, int side, bool sg_keys) {
+    return kRowstepBlockmin && kind == BM_SAD && nw == 1 && side == SIDE_LEFT && !sg_keys && radius <= 5;
+}
+
 // Arguments of the fused pass kernel bm2 (dsx_bm.hip).
 struct Bm2Args {
     const uint8_t *ref;  // reference image (L for left/volume passes, R for the right pass)
@@ -64,6 +78,29 @@ struct VolArgs {
 };
 
 constexpr int kStripWidth = 32;  // TX of bm2
+
+// The minimum of the eight u16 costs of a 16-byte tile block.  Integer form: three v_pk_min_u16 and the low against
+// the high half.  F16 form: v_pk_minimum3_f16 of three words, one v_pk_min_u16 with the fourth, then the halves - one
+// packed op fewer.  For costs below 0x7C00 only: as f16 bit patterns those are finite and non-negative, which order as
+// the integers do, and kernels run with f16 denormals kept (float_denorm_mode_16_64 = 3), so patterns below 0x0400
+// are not flushed.  v_pk_minimum3_f16 issues in 4.12 cycles, as v_pk_min_u16 does (tools/ubench3.hip).  The nested
+// llvm.minimum is how the instruction is named: gfx950 selects it as one op (tools/rowloop_isa.py counts them), and
+// unlike an asm statement it leaves the block's 16-byte LDS read whole (the asm form read 12 + 4 bytes and spilled).
+template <bool F16>
+__device__ __forceinline__ uint32_t block_min8(uint4 v) {
+    typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+    typedef _Float16 hf2 __attribute__((ext_vector_type(2)));
+    us2 mm;
+    if constexpr (F16) {
+        const hf2 m3 = __builtin_elementwise_minimum(
+            __builtin_elementwise_minimum(__builtin_bit_cast(hf2, v.x), __builtin_bit_cast(hf2, v.y)), __builtin_bit_cast(hf2, v.z));
+        mm = __builtin_elementwise_min(__builtin_bit_cast(us2, m3), __builtin_bit_cast(us2, v.w));
+    } else {
+        mm = __builtin_elementwise_min(__builtin_elementwise_min(__builtin_bit_cast(us2, v.x), __builtin_bit_cast(us2, v.y)),
+                                       __builtin_elementwise_min(__builtin_bit_cast(us2, v.z), __builtin_bit_cast(us2, v.w)));
+    }
+    return mm.x < mm.y ? mm.x : mm.y;
+}
 
 // q = trunc(num / den2) (C semantics), den2 > 0, |q| small (the sub-pixel correction): float
 // reciprocal estimate + exact integer fix-up; replaces the ~40-instruction integer division.

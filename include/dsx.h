@@ -32,7 +32,8 @@
 extern "C" {
 #endif
 
-#define DSX_VERSION 106 /* additive since 1.0.6 (layouts unchanged): dsx_upsample, dsx_default_upsample,
+#define DSX_VERSION 106 /* additive since 1.0.6 (layouts unchanged): dsx_block_min8_device (the fused SAD pass's
+                           block minimum alone, for tests); dsx_upsample, dsx_default_upsample,
                            dsx_check_upsample, dsx_upsample_taps, dsx_upsample_x0, dsx_upsample_device
                            (joint bilateral upsampling of a downscaled run's map to the full-size frame);
                            dsx_temporal_params, dsx_default_temporal,
@@ -226,6 +227,11 @@ int dsx_texture_sum_device(const void *d_pref, int32_t H, int32_t W, int64_t str
  * `cost` (DSX_COST_CENSUS9X7: 62 bits, DSX_COST_CENSUS5X5: 24 bits; the upper bits 0). */
 int dsx_census_device(const void *d_img, int32_t H, int32_t W, int64_t stride_bytes, int32_t cost, void *d_out_u64,
                       void *hip_stream);
+
+/* The fused SAD pass's block minimum in its packed-f16 form, alone (stateless, asynchronous on hip_stream; for
+ * tests): d_blocks n 16-byte blocks of eight uint16 costs, each below 0x7C00 -> d_out_u32[i] = the minimum of block
+ * i's eight costs, taken as the pass takes it (v_pk_minimum3_f16 of three words, integer minima of the rest). */
+int dsx_block_min8_device(const void *d_blocks, int64_t n, void *d_out_u32, void *hip_stream);
 
 /* Matcher confidence map and confidence threshold.  An addition of this build (as the prefilter and the
  * census costs are): parity with nothing outside this repository is claimed.

@@ -218,6 +218,10 @@ def report(asm, name, out):
         out(f"    sums: v_sad_u8 {cnt('v_sad_u8')}, v_sad_hi_u8 {cnt('v_sad_hi_u8')}, v_sub_u32 {cnt('v_sub_u32')}, "
             f"v_add_u32 {cnt('v_add_u32')}, v_add3_u32 {cnt('v_add3_u32')}, v_perm_b32 {cnt('v_perm_b32')}, "
             f"v_mov_b32_dpp {cnt('v_mov_b32_dpp')}")
+        # the tail's block keys by opcode: block minima (packed, then low against high half), key forms, running key
+        out(f"    keys: v_pk_min_u16 {cnt('v_pk_min_u16')}, v_pk_minimum3_f16 {cnt('v_pk_minimum3_f16')}, "
+            f"v_min_u16 {cnt('v_min_u16')}, v_lshl_or_b32 {cnt('v_lshl_or_b32')}, v_min_u32 {cnt('v_min_u32')}, "
+            f"v_min3_u32 {cnt('v_min3_u32')}")
         # The compiler lays the blocks of a step out of program order (the column update and the
         # box phase sit behind the stores in the listing), so positions are taken from the control
         # flow: op k leads to op k + 1 (unless it is s_branch) and to its branch target.  The step

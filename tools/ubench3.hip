@@ -58,6 +58,26 @@ DEF2(k_bcnt_u32_b32, "v_bcnt_u32_b32")
 DEF2(k_xor_b32, "v_xor_b32")
 DEF3(k_lshl_add_u32, "v_lshl_add_u32")
 DEF3(k_alignbit_b32, "v_alignbit_b32")
+// the three-input packed f16 minimum of the fused pass's block minima (dsx_bm.hip, emin8)
+DEF3(k_pk_minimum3_f16, "v_pk_minimum3_f16")
+
+// One dependent chain per wave: 16 INS in a row, each reading the one before.  PAD is what hipcc puts between such a
+// pair ("s_nop 0\n\t" behind a v_pk_* producer on gfx950, "" where there is no hazard), so the row prices the
+// pair as the row loop executes it.
+#define DEFD(NAME, INS, PAD)                                                                       \
+  __global__ void NAME(uint32_t *out, uint32_t seed) {                                             \
+    uint32_t a0 = seed + threadIdx.x, b = seed * 3 + 1;                                            \
+    for (int i = 0; i < N_OUTER; ++i) {                                                            \
+      asm volatile(INS " %0, %0, %1\n\t" PAD INS " %0, %0, %1\n\t" PAD INS " %0, %0, %1\n\t" PAD INS " %0, %0, %1\n\t" PAD \
+                   INS " %0, %0, %1\n\t" PAD INS " %0, %0, %1\n\t" PAD INS " %0, %0, %1\n\t" PAD INS " %0, %0, %1\n\t" PAD \
+                   INS " %0, %0, %1\n\t" PAD INS " %0, %0, %1\n\t" PAD INS " %0, %0, %1\n\t" PAD INS " %0, %0, %1\n\t" PAD \
+                   INS " %0, %0, %1\n\t" PAD INS " %0, %0, %1\n\t" PAD INS " %0, %0, %1\n\t" PAD INS " %0, %0, %1\n\t" PAD \
+                   "s_nop 0" : "+v"(a0) : "v"(b));                                                 \
+    }                                                                                              \
+    out[blockIdx.x * blockDim.x + threadIdx.x] = a0;                                               \
+  }
+DEFD(k_dep_pk_min_u16, "v_pk_min_u16", "s_nop 0\n\t")
+DEFD(k_dep_min_u32, "v_min_u32", "")
 
 // 64-bit accumulator forms: INS d[2], s0[2], s1, d[2] (quad SAD) or d[2], s0[2], s1[2] (packed f32)
 #define DEFQ(NAME, INS, TAIL)                                                                      \
@@ -108,10 +128,11 @@ int main() {
     {"v_perm_b32", k_perm_b32}, {"v_pk_mad_u16", k_pk_mad_u16}, {"v_mad_u32_u24", k_mad_u32_u24},
     {"v_msad_u8", k_msad_u8}, {"v_sad_hi_u8", k_sad_hi_u8}, {"v_qsad_pk_u16_u8", k_qsad}, {"v_mqsad_pk_u16_u8", k_mqsad},
     {"v_pk_add_f32", k_pk_add_f32}, {"v_pk_mul_f32", k_pk_mul_f32}, {"v_bcnt_u32_b32", k_bcnt_u32_b32},
-    {"v_xor_b32", k_xor_b32}, {"v_lshl_add_u32", k_lshl_add_u32}, {"v_alignbit_b32", k_alignbit_b32}};
+    {"v_xor_b32", k_xor_b32}, {"v_lshl_add_u32", k_lshl_add_u32}, {"v_alignbit_b32", k_alignbit_b32},
+    {"v_pk_minimum3_f16", k_pk_minimum3_f16}, {"dep v_pk_min_u16+nop", k_dep_pk_min_u16}, {"dep v_min_u32", k_dep_min_u32}};
   for (auto &x : ks) {
     const float ms = time_kernel(x.k, buf, blocks, threads);
-    printf("%-16s %7.3f ms  %.2f cycles per wave-instr per SIMD (at 2.4 GHz)\n", x.n, ms, ms * 1e-3 * 2.4e9 * 1024 / wi);
+    printf("%-20s %7.3f ms  %.2f cycles per wave-instr per SIMD (at 2.4 GHz)\n", x.n, ms, ms * 1e-3 * 2.4e9 * 1024 / wi);
   }
   return 0;
 }
