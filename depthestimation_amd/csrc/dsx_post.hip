@@ -731,7 +731,7 @@ __device__ bool spk_small(const PostFullArgs &a, int k0, int *vis, int lane, int
             }
             int h = -1;
             bool large = false;
-            if (e >= 0) {
+            if (e != -1) {  // (y << 16) | x is negative from row 32768 on; y, x < 65535, so never -1
                 const int y = (int)((unsigned)e >> 16), x = e & 0xFFFF;
                 const int c = spk_code(a, (int64_t)y * Wc + x);
                 if (c < kPend) large = true;  // a decided piece with a joining edge: more than max pixels
